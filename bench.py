@@ -10,9 +10,12 @@ LibriSpeech-100h hybrid CTC+attention, ctc_weight 0.5, bf16, 1 GPU), c2 (configs
 (configs[3]: V=5000, L_max=60), c5 (configs[4]: 6x1024 pBLSTM, V=5000), c1 (configs[0]: timit_example.yaml shapes, fp32
 MFMA), libri_vgg / libri_vgg_max (the reference's shipped config/libri_example.yaml with its VGG front-end).
 `value` is measured with the batches resident in HBM when the timed region starts; the same loop fed from pinned host
-memory (the H2D copy of SURVEY.md §8d inside the timed region) is reported beside it as config.value_incl_h2d.
-Prints ONE JSON line (rank 0) with `roofline` (the dominant single kernel, live HIP-event timing) and `cpu_baseline`
-(the CPU oracle timed on this host on a bounded sample of the same workload)."""
+memory (the H2D copy of SURVEY.md §8d inside the timed region) is reported beside it as config.value_incl_h2d (--full).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints that line; `--full` adds
+that H2D-inclusive loop, `roofline` (the dominant single kernel, live HIP-event timing) and `cpu_baseline` (the CPU oracle
+timed on this host on a bounded sample of the same workload).  `--dump-outputs DIR` writes what the last timed step
+computed (losses, logits, gradient norm, updated parameters) as DIR/<name>.npy, so that two builds can be compared on the
+same seeded inputs."""
 import argparse
 import importlib
 import json
@@ -180,8 +183,12 @@ def main():
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=15)
     ap.add_argument('--workload', default='c3', choices=sorted(WORKLOADS))
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    # CPU baseline sample: 8 utterances of the step-0 batch, one untimed + 3 timed full train steps (~5 s each on 16 cores at c3)
+    ap.add_argument('--full', action='store_true',
+                    help='also run the H2D-inclusive loop, the per-kernel roofline pass and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip the CPU baseline')
+    # (--full) CPU baseline sample: 8 utterances of the step-0 batch, one untimed + 3 timed full train steps (~5 s each on 16 cores at c3)
     ap.add_argument('--cpu-sample-b', type=int, default=8)
     ap.add_argument('--cpu-steps', type=int, default=3)
     a = ap.parse_args()
@@ -215,15 +222,18 @@ def main():
     t.set_model()
     dev = t.device
     # pre-stage distinct batches (per-step seed = 1234 + global batch index; each rank its own shard): in HBM for the
-    # timed region behind `value`, and in pinned host memory for the H2D-inclusive loop
+    # timed region behind `value`, and (--full) in pinned host memory for the H2D-inclusive loop
     # (no more distinct batches than warm-up steps: every staged shape has been through the allocator before the timed region)
     n_stage = max(1, min(8, a.warmup, a.steps + a.warmup))
     staged, pinned = [], []
     for i in range(n_stage):
         x, y, lens = synth.make_batch(i * world + rank, w['B'], w['T_max'], w['D'], w['V'], w['L_max'], tr, ctc=w['ctc'] > 0)
         staged.append((x.to(dev), y.to(dev), sum(lens), (lens, int((y != 0).sum(-1).max()))))
-        pinned.append((x.pin_memory(), y.pin_memory()))
+        if a.full:
+            pinned.append((x.pin_memory(), y.pin_memory()))
     t.asr_opt.zero_grad()
+
+    last = {}
 
     def run(k0, k, known_lengths=False, from_host=False):
         frames = 0
@@ -237,7 +247,7 @@ def main():
                     ready.record(ops.copy_stream())
                 for v in (x, y):
                     v.record_stream(torch.cuda.current_stream())
-            t.train_step(x, y, 1.0, host_lens=hl if known_lengths else None, inputs_ready=ready)
+            last['out'] = t.train_step(x, y, 1.0, host_lens=hl if known_lengths else None, inputs_ready=ready)
             frames += f
         return frames
 
@@ -268,6 +278,61 @@ def main():
         dt, frames = float(tmax), float(fsum)
     assert int(t.asr_model.status.item()) == 0, 'persistent LSTM hand-off timed out'
     skipped = bool(t.asr_opt.norm3[2].item())
+    note(f'{dt * 1e3 / a.steps:.1f} ms/step')
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, t, last['out'])
+    if a.full:
+        full_extras(a, w, cfg, t, run, barrier, world, rank, dt, frames, skipped)
+    elif rank == 0:
+        print(json.dumps(result_line(a, w, t, world, dt, frames, skipped)), flush=True)
+    if world > 1:
+        torch.distributed.barrier()
+        torch.distributed.destroy_process_group()
+
+
+def result_line(a, w, t, world, dt, frames, skipped):
+    return {
+        'metric': 'mel-frames/sec per train step (LAS+CTC, 80-dim fbank)' if w['ctc'] > 0 else
+                  'mel-frames/sec per train step (LAS attention-only, 80-dim fbank)',
+        'value': frames / dt, 'unit': 'mel-frames/s',
+        'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': dt * 1e3 / a.steps,
+        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+        'dtype': 'bf16' if w['prec'] == 'bf16' else 'f32', 'data': 'synthetic',
+        'config': {'workload': f"{a.workload}: {w['name']}", 'per_gpu_batch': w['B'], 'global_batch': w['B'] * world,
+                   'T_max': w['T_max'], 'L_max': w['L_max'], 'D': w['D'], 'V': w['V'], 'optimizer': w['opt'][0],
+                   'joint_ctc': w['ctc'], 'params': int(t.asr_model.n_params), 'parallelism': f'dp{world}',
+                   'nan_skipped_last_step': skipped},
+    }
+
+
+DUMP_MAX_ELEMS = 4 << 20          # per array (16 MB of float32): larger outputs are dumped as a fixed, seeded sample
+
+
+def dump_outputs(out_dir, t, out):
+    """What the caller of Trainer.train_step receives from the last timed step -- the joint / attention / CTC losses and
+    the attention logits -- plus the optimiser's outcome: the gradient norm before clipping and the updated parameters.
+    An array above DUMP_MAX_ELEMS is dumped as a sample: the elements at the sorted, de-duplicated indices of
+    np.random.default_rng(0).integers(0, numel, DUMP_MAX_ELEMS), the same for every run and build at the same shape."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    loss, att_loss, ctc_loss, att_pred, _ = out
+    arrays = {'loss': loss, 'att_loss': att_loss, 'ctc_loss': ctc_loss, 'grad_norm': t.asr_opt.norm3[0],
+              'att_logits': att_pred, 'params': t.asr_model.flat_params}
+    for name, v in arrays.items():
+        if v is None:
+            continue
+        v = v.detach().float()
+        if v.numel() > DUMP_MAX_ELEMS:
+            idx = np.unique(np.random.default_rng(0).integers(0, v.numel(), DUMP_MAX_ELEMS))
+            v = v.reshape(-1)[torch.from_numpy(idx).to(v.device)]
+        np.save(os.path.join(out_dir, f'{name}.npy'), v.cpu().numpy().astype(np.float32))
+    note(f'outputs of the last timed step written to {out_dir}')
+
+
+def full_extras(a, w, cfg, t, run, barrier, world, rank, dt, frames, skipped):
+    """--full: the H2D-inclusive loop, the per-kernel roofline pass and the CPU baseline, added to the result line."""
+    ops = importlib.import_module('end-to-end-asr-pytorch_amd.ops')
+    dev = t.device
     # the same loop with the batch coming from pinned host memory inside the timed region (SURVEY.md 8d)
     barrier()
     t1 = time.perf_counter()
@@ -280,7 +345,7 @@ def main():
         torch.distributed.all_reduce(stat_h[1:2], op=torch.distributed.ReduceOp.SUM)
     dt_h, frames_h = float(stat_h[0]), float(stat_h[1])
 
-    note(f'{dt * 1e3 / a.steps:.1f} ms/step; kernel timing pass')
+    note('kernel timing pass')
     # ---- roofline of the dominant kernel: live HIP-event timing of its launches over 3 more steps
     # The brackets are HIP events on the launch stream, so a bracket also counts any time the GPU waits for the host
     # to enqueue the next kernel.  Each timed step therefore starts with a ~25 ms device-side sleep: the host (≈6 ms
@@ -298,27 +363,13 @@ def main():
     attach_pmc_traffic(roof, a.workload)
 
     if rank == 0:
-        out = {
-            'metric': 'mel-frames/sec per train step (LAS+CTC, 80-dim fbank)' if w['ctc'] > 0 else
-                      'mel-frames/sec per train step (LAS attention-only, 80-dim fbank)',
-            'value': frames / dt, 'unit': 'mel-frames/s',
-            'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': dt * 1e3 / a.steps,
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-            'dtype': 'bf16' if w['prec'] == 'bf16' else 'f32', 'data': 'synthetic',
-            'config': {'workload': f"{a.workload}: {w['name']}", 'per_gpu_batch': w['B'], 'global_batch': w['B'] * world,
-                       'T_max': w['T_max'], 'L_max': w['L_max'], 'D': w['D'], 'V': w['V'], 'optimizer': w['opt'][0],
-                       'joint_ctc': w['ctc'], 'params': int(t.asr_model.n_params), 'parallelism': f'dp{world}',
-                       'nan_skipped_last_step': skipped, 'value_incl_h2d': frames_h / dt_h,
-                       'ms_per_step_incl_h2d': dt_h * 1e3 / a.steps},
-            'roofline': roof,
-        }
+        out = result_line(a, w, t, world, dt, frames, skipped)
+        out['config'].update(value_incl_h2d=frames_h / dt_h, ms_per_step_incl_h2d=dt_h * 1e3 / a.steps)
+        out['roofline'] = roof
         if world == 1 and not a.no_cpu_baseline:
             note('cpu baseline (oracle on host cores)')
             out['cpu_baseline'] = cpu_baseline(w, cfg, a.cpu_sample_b, a.cpu_steps)
         print(json.dumps(out), flush=True)
-    if world > 1:
-        torch.distributed.barrier()
-        torch.distributed.destroy_process_group()
 
 
 if __name__ == '__main__':

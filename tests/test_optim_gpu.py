@@ -19,6 +19,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN, ROOT
+from golden_npz import load as load_golden
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -48,7 +49,7 @@ def one_iteration(ops, model, opt, x, y, w):
 def test_three_optimizer_steps_vs_reference(las, name, prec):
     ops, asr, optim = las
     from gen_golden import TINY
-    d = np.load(os.path.join(GOLDEN, f'g3_step_{name}.npz'))
+    d = load_golden(f'g3_step_{name}.npz')
     cfg = TINY[name]
     x = torch.tensor(d['x'], device=DEV)
     y = torch.tensor(d['y'], device=DEV)

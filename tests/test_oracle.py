@@ -10,10 +10,11 @@ from oracle import las_ref as R
 from oracle.ctc_c import ctc_ref
 
 from conftest import GOLDEN
+from golden_npz import load as load_golden
 
 
 def G(name):
-    return np.load(os.path.join(GOLDEN, name))
+    return load_golden(name)
 
 
 def W_of(d, prefix='w.'):

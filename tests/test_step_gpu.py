@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN, ROOT
+from golden_npz import load as load_golden
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -28,7 +29,7 @@ def las():
 def test_step_vs_reference(las, name, prec):
     ops, asr = las
     from gen_golden import TINY
-    d = np.load(os.path.join(GOLDEN, f'g3_step_{name}.npz'))
+    d = load_golden(f'g3_step_{name}.npz')
     cfg = TINY[name]
     x = torch.tensor(d['x'], device=DEV)
     y = torch.tensor(d['y'], device=DEV)

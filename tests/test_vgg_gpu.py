@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN
+from golden_npz import load as load_golden
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -58,7 +58,7 @@ def run_case(mods, prec, x_np, W_np, gy_np, time_major=False):
 @pytest.mark.parametrize('prec', ['f32', 'bf16'])
 @pytest.mark.parametrize('name', ['mfcc26', 'fbank40'])
 def test_vgg_golden(mods, name, prec, time_major):
-    d = np.load(os.path.join(GOLDEN, f'g1_vgg_{name}.npz'))
+    d = load_golden(f'g1_vgg_{name}.npz')
     W = {k[2:]: d[k] for k in d.files if k.startswith('w.')}
     y, gx, gw = run_case(mods, prec, d['x'], W, d['gy'], time_major)
     near(y, d['y'], prec, 'y')

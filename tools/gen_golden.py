@@ -27,6 +27,9 @@ import tempfile
 import numpy as np
 import torch
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tests'))
+from golden_npz import save as save_golden      # np.savez, in parts of < 1 MiB
+
 REF = '/root/reference'
 
 
@@ -123,7 +126,7 @@ def g1_rnnlayer(asr, out):
              'gy': _np(gy), 'gx': _np(x.grad), 'sr': np.array(sr), 'bidir': np.array(int(bidir))}
         d.update(_state(layer, 'w.'))
         d.update(_grads(layer))
-        np.savez(os.path.join(out, f'g1_rnnlayer_{name}.npz'), **d)
+        save_golden(os.path.join(out, f'g1_rnnlayer_{name}.npz'), **d)
 
 
 def g1_listener(asr, out):
@@ -141,7 +144,7 @@ def g1_listener(asr, out):
          'gy': _np(gy), 'gx': _np(x.grad)}
     d.update(_state(enc, 'w.'))
     d.update(_grads(enc))
-    np.savez(os.path.join(out, 'g1_listener.npz'), **d)
+    save_golden(os.path.join(out, 'g1_listener.npz'), **d)
 
 
 def g1_vgg(asr, out):
@@ -158,7 +161,7 @@ def g1_vgg(asr, out):
         d = {'x': _np(x), 'lens': np.array(lens), 'y': _np(y), 'out_lens': np.array(olen), 'gy': _np(gy), 'gx': _np(x.grad)}
         d.update(_state(vgg, 'w.'))
         d.update(_grads(vgg))
-        np.savez(os.path.join(out, f'g1_vgg_{name}.npz'), **d)
+        save_golden(os.path.join(out, f'g1_vgg_{name}.npz'), **d)
 
 
 def g1_attention(asr, out):
@@ -187,7 +190,7 @@ def g1_attention(asr, out):
             d[f'gc{i}'] = _np(gc[i]); d[f'gs{i}'] = _np(gs[i])
         d.update(_state(att, 'w.'))
         d.update(_grads(att))
-        np.savez(os.path.join(out, f'g1_attention_{mode}.npz'), **d)
+        save_golden(os.path.join(out, f'g1_attention_{mode}.npz'), **d)
 
 
 def g1_speller(asr, out):
@@ -208,7 +211,7 @@ def g1_speller(asr, out):
             d[f'out{i}'] = _np(outs[i]); d[f'go{i}'] = _np(go[i])
         d.update(_state(sp, 'w.'))
         d.update(_grads(sp))
-        np.savez(os.path.join(out, f'g1_speller_l{nl}.npz'), **d)
+        save_golden(os.path.join(out, f'g1_speller_l{nl}.npz'), **d)
 
 
 # ----------------------------------------------------------------------------- G2 CTC
@@ -236,7 +239,7 @@ def g2_ctc(out):
         loss = torch.nn.CTCLoss(blank=0, reduction='mean')(lp, label, torch.LongTensor(enc_len), tgt_len)
         loss.backward()
         nll, log_alpha = torch._ctc_loss(lp.detach(), label, enc_len, tgt_len.tolist(), 0, False)
-        np.savez(os.path.join(out, f'g2_ctc_{name}.npz'),
+        save_golden(os.path.join(out, f'g2_ctc_{name}.npz'),
                  logits=_np(logits), label=_np(label), enc_len=np.array(enc_len), tgt_len=_np(tgt_len),
                  loss=_np(loss), nll=_np(nll), log_alpha=_np(log_alpha), glogits=_np(logits.grad))
 
@@ -355,7 +358,7 @@ def g3_steps(asr, out):
             x, y, lens = _synth_batch(4, 17, 5, V, 4, gen)
         rec = ref_step(asr, cfg, x, y, V, n_opt_steps=3)
         rec.update({'x': _np(x), 'y': _np(y), 'lens': np.array(lens), 'V': np.array(V)})
-        np.savez(os.path.join(out, f'g3_step_{name}.npz'), **rec)
+        save_golden(os.path.join(out, f'g3_step_{name}.npz'), **rec)
 
 
 def g9_sched_sampling(asr, out):
@@ -381,7 +384,7 @@ def g9_sched_sampling(asr, out):
                     'flip_values': np.array(record['flip_values'], np.float64),
                     'draw_step': np.array([t for t, _ in record['draws']], np.int64),
                     'draw_tokens': np.stack([_np(tok) for _, tok in record['draws']]).astype(np.int64)})
-        np.savez(os.path.join(out, f'g9_sched_{name}.npz'), **rec)
+        save_golden(os.path.join(out, f'g9_sched_{name}.npz'), **rec)
 
 
 # ----------------------------------------------------------------------------- G4 trainer trace
@@ -449,7 +452,7 @@ def g4_trace(Writer, out):
         rec[f'{split}_y'] = np.concatenate([np.array(v) for v in ys])
     rec['V'] = np.array(V)
     rec.update(_state(t.asr_model, 'w_after.'))
-    np.savez(os.path.join(out, 'g4_trainer_trace.npz'), **rec)
+    save_golden(os.path.join(out, 'g4_trainer_trace.npz'), **rec)
     import json
     json.dump(cfg, open(os.path.join(out, 'g4_config.json'), 'w'), indent=1)
 
@@ -468,7 +471,7 @@ def g5_prefix(out):
     psi2, r2 = sc.cheap_compute(g, r1[cand.index(3)], cand)      # includes the repeat-token quirk (3 in cand)
     g = [3, 3]
     psi3, r3 = sc.cheap_compute(g, r2[cand.index(3)], [2, 3, 5])
-    np.savez(os.path.join(out, 'g5_ctc_prefix.npz'), lp=_np(lp), r0=r0, psi1=psi1, r1=r1, psi2=psi2, r2=r2,
+    save_golden(os.path.join(out, 'g5_ctc_prefix.npz'), lp=_np(lp), r0=r0, psi1=psi1, r1=r1, psi2=psi2, r2=r2,
              psi3=psi3, r3=r3)
 
 
@@ -497,7 +500,7 @@ def g6_beam(asr, out):
                 d[f'hyp{i}.seq'] = np.array(h.outIndex, dtype=np.int64)
                 d[f'hyp{i}.scores'] = np.array([float(v) for v in h.output_scores], dtype=np.float64)
             d.update(_state(model, 'w.'))
-            np.savez(os.path.join(out, f'g6_beam_{name}_b{beam}.npz'), **d)
+            save_golden(os.path.join(out, f'g6_beam_{name}_b{beam}.npz'), **d)
 
 
 
@@ -602,7 +605,7 @@ def g7_valid(Writer, out):
             rec[f'{split}_ylen'] = np.array([len(v) for v in ys])
             rec[f'{split}_y'] = np.concatenate([np.array(v) for v in ys])
         rec['V'] = np.array(V)
-        np.savez(os.path.join(out, f'g7_valid_{name}.npz'), **rec)
+        save_golden(os.path.join(out, f'g7_valid_{name}.npz'), **rec)
         json.dump(cfg, open(os.path.join(out, f'g7_config_{name}.json'), 'w'), indent=1)
         return rec
 
@@ -666,7 +669,7 @@ def g8_libri(out):
     ds = LoadDataset('test', text_only=False, **solver).dataset
     rec['test_beam.files'] = np.array([v[0] for v in ds.X])
     rec['D'] = np.array(D)
-    np.savez(os.path.join(out, 'g8_libri_buckets.npz'), **rec)
+    save_golden(os.path.join(out, 'g8_libri_buckets.npz'), **rec)
 
 
 def main():

@@ -13,13 +13,13 @@ part=${1:-a}
 if [ "$part" = a ]; then
   timeout -k 10 900 python -m pytest tests -q -x -m gpu > $O/tests.log 2>&1 || { tail -30 $O/tests.log; exit 1; }
   tail -1 $O/tests.log
-  timeout -k 10 500 python bench.py --cpu-steps 3 > $O/bench_c3.json 2> $O/bench_c3.err || { tail $O/bench_c3.err; exit 2; }
+  timeout -k 10 500 python bench.py --full --cpu-steps 3 > $O/bench_c3.json 2> $O/bench_c3.err || { tail $O/bench_c3.err; exit 2; }
   cut -c1-300 $O/bench_c3.json
   for w in c2 c4 c5 libri_vgg; do
-    timeout -k 10 300 python bench.py --workload $w --no-cpu-baseline > $O/bench_$w.json 2> $O/bench_$w.err || { tail $O/bench_$w.err; exit 3; }
+    timeout -k 10 300 python bench.py --full --workload $w --no-cpu-baseline > $O/bench_$w.json 2> $O/bench_$w.err || { tail $O/bench_$w.err; exit 3; }
     cut -c1-200 $O/bench_$w.json
   done
-  timeout -k 10 300 python bench.py --workload c1 --cpu-sample-b 8 --cpu-steps 5 > $O/bench_c1.json 2> $O/bench_c1.err || { tail $O/bench_c1.err; exit 4; }
+  timeout -k 10 300 python bench.py --full --workload c1 --cpu-sample-b 8 --cpu-steps 5 > $O/bench_c1.json 2> $O/bench_c1.err || { tail $O/bench_c1.err; exit 4; }
   cut -c1-200 $O/bench_c1.json
 elif [ "$part" = b ]; then
   for w in c3 c5 c1 c2 c4; do

@@ -248,6 +248,12 @@ class Seq2Seq(nn.Module):
         from .beam import beam_decode
         return beam_decode(self, audio_feature, decode_step, state_len, decode_beam_size)
 
+    def beam_decode_batch(self, audio_feature, decode_steps, state_len, decode_beam_size):
+        """The same for U utterances in one call (audio_feature [U,T,D], decode_steps an int or one per utterance), with the
+        beam loop kept on the device: list[list[Hypothesis]]."""
+        from .beam import beam_decode_batch
+        return beam_decode_batch(self, audio_feature, decode_steps, state_len, decode_beam_size)
+
     # -- full forward ----------------------------------------------------------------------------------------
     def forward(self, audio_feature, decode_step, tf_rate=0.0, teacher=None, state_len=None, state_len_dev=None, replay=None):
         """reference asr.py:58-112.  Returns (ctc_output [B,T',V]|None, encode_len list[int],

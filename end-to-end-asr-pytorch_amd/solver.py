@@ -379,7 +379,8 @@ class Trainer(Solver):
 class Tester(Solver):
     """Handler for the complete inference progress; reference src/solver.py:293-441.  Beam search keeps the
     reference's batch size of 1 utterance, but every hypothesis of the beam (and every CTC candidate) advances in one
-    batched device step (beam.py), so --njobs is accepted and unused."""
+    batched device step (beam.py), so --njobs is accepted and unused.  solver.decode_batch_size > 1 (not in the reference)
+    decodes that many consecutive utterances per call with the beam loop kept on the device (beam.beam_decode_batch)."""
 
     def __init__(self, config, paras):
         super().__init__(config, paras)
@@ -446,14 +447,24 @@ class Tester(Solver):
         self.verbose('Start decoding with beam search, beam size = ' + str(self.decode_beam_size))
         self.verbose('Number of utts to decode : {}'.format(len(self.test_set)))
         n = 0
+        U = int(self.config['solver'].get('decode_batch_size', 1))
+        pending = []                                 # decode_batch_size > 1: consecutive utterances waiting for a full batch
         for x, y in self.test_set:
             if len(x.shape) == 4:
                 x = x.squeeze(0)
             if len(y.shape) == 3:
                 y = y.squeeze(0)
             for b in range(x.shape[0]):
-                self.beam_decode(x[b:b + 1], y[b].tolist())
+                if U > 1:
+                    pending.append((x[b:b + 1], y[b].tolist()))
+                    if len(pending) == U:
+                        self.beam_decode_batch(pending)
+                        pending = []
+                else:
+                    self.beam_decode(x[b:b + 1], y[b].tolist())
                 n += 1
+        if pending:
+            self.beam_decode_batch(pending)
         self.verbose('Decode done, best results at {}.'.format(os.path.join(self.ckpdir, self.decode_file + '.txt')))
         self.verbose('Top {} results at {}.'.format(self.decode_beam_size,
                                                     os.path.join(self.ckpdir, self.decode_file + '_nbest.txt')))
@@ -477,6 +488,21 @@ class Tester(Solver):
         hyps = self.asr_model.beam_decode(x, max_decode_step, state_len, self.decode_beam_size)
         self._check_status(None, 'beam decoding')
         self.write_hyp(hyps, y)
+        return hyps
+
+    def beam_decode_batch(self, utts):
+        """solver.decode_batch_size > 1: the same for several utterances [(x [1,T,D], y)] in one device-resident beam loop
+        (beam.beam_decode_batch); results are written in the order given."""
+        xs = [x.to(device=self.device, dtype=torch.float32) for x, _ in utts]
+        lens = [ops.infer_lengths(x).cpu().tolist()[0] for x in xs]
+        batch = torch.zeros(len(xs), max(lens), xs[0].shape[-1], dtype=torch.float32, device=self.device)
+        for u, (x, n) in enumerate(zip(xs, lens)):
+            batch[u, :n] = x[0, :n]                   # (a VGG model encodes each utterance trimmed to its own frames)
+        steps = [int(math.ceil(n * self.decode_step_ratio)) for n in lens]
+        hyps = self.asr_model.beam_decode_batch(batch, steps, lens, self.decode_beam_size)
+        self._check_status(None, 'beam decoding')
+        for (_, y), h in zip(utts, hyps):
+            self.write_hyp(h, y)
         return hyps
 
 

@@ -360,6 +360,53 @@ int las_ctc_prefix_score(const float* lp, int T, int V, const float* r_prev, con
 int las_beam_combine(float* cur, int N, int V, const int32_t* cand, const float* psi, const float* prev_ctc, int K,
                      float ctc_weight, void* stream);
 
+/* ---- batched beam search: U utterances x beam slots, the beam loop kept on the device --------------
+ * Rows are r = u*beam + slot.  Every step runs las_decoder_step / las_log_softmax_rows / las_topk_rows /
+ * las_beam_combine over all U*beam rows, then las_beam_select and las_beam_gather; nothing is read back until
+ * the loop has been enqueued.  Rows of dead slots (slot >= n_live[u]) and of utterances past their step limit are
+ * computed and ignored: no kernel below reads them into a live row.
+ *
+ * CTCPrefixScore (src/ctc.py:19-27, 65-101) over several utterances: lp [U][Tmax][V], T_u [U] the valid frames
+ * of each utterance (1 <= T_u <= Tmax).  init: r0 [U][Tmax][2], frames t < T_u written.  score: row_utt [N] maps a
+ * row to its utterance (0 <= row_utt < U); r_prev [N][Tmax][2], cand [N][K] -> psi [N][K], r_out [N][K][Tmax][2]; a row's recursion
+ * and its psi sum stop at its own T_u (frames t >= T_u of r_out are left untouched).  Arithmetic and the
+ * cand == last_tok treatment are those of las_ctc_prefix_score. */
+int las_ctc_prefix_init_batch(const float* lp, int U, int Tmax, int V, const int32_t* T_u, float* r0, void* stream);
+int las_ctc_prefix_score_batch(const float* lp, int U, int Tmax, int V, const int32_t* T_u, const int32_t* row_utt,
+                               const float* r_prev, const int32_t* last_tok, const int32_t* prefix_len,
+                               const int32_t* cand, int N, int K, float* psi, float* r_out, void* stream);
+/* One step of the hypothesis bookkeeping for every utterance (Hypothesis.addTopk, src/postprocess.py:71-104, and the
+ * ranking of src/asr.py:237-252), one workgroup per utterance.  topv / topi [U*beam][kb]: the step's top-kb scores and
+ * tokens of every row; cand [U*beam][K] the CTC candidate lists (NULL without CTC: j = 0).  Slot state: n_live [U],
+ * sum [U*beam] (fp64 running sum of the hypothesis' scores, added in sequence order as Python's sum()), plen
+ * [U*beam].  Candidates are taken from live slots in slot order, then i ascending; token 1 (<eos>) is not expanded,
+ * its score is the slot's termination score.  They are ranked by (sum + score) / (plen + 1) (one fp64 divide),
+ * descending, ties to the earlier candidate (a stable sort), and the first `beam` become the new slots:
+ *   parent / tok_new / j_new / plen_new [U*beam], sum_new [U*beam] (fp64), n_new [U]
+ * (j_new: index of the token in the parent's candidate list).  An utterance with step >= limit[u] is left alone
+ * (n_new[u] = n_live[u], nothing recorded); beam = 1 ends at the first <eos> and an utterance whose every candidate
+ * was <eos> ends too (both: n_new = 0, asr.py:246-247).
+ * rec: this step's trellis record, 5*U*beam + U 32-bit words:
+ *   tok [U*beam] | parent [U*beam] | score [U*beam] (float) | terminated [U*beam] | term score [U*beam] (float) | n_new [U]
+ * the first three per NEW slot, the next two per OLD slot; n_new is -1 for an utterance past its limit.
+ * beam*(kb*20 + K*4) B of LDS must fit (<= 60 KB). */
+int las_beam_select(const float* topv, const int32_t* topi, const int32_t* cand, int U, int beam, int kb, int K,
+                    const int32_t* n_live, const double* sum, const int32_t* plen, const int32_t* limit, int step,
+                    int32_t* parent, int32_t* tok_new, int32_t* j_new, int32_t* plen_new, double* sum_new,
+                    int32_t* n_new, int32_t* rec, void* stream);
+/* Reorders the state by parent for every utterance in one launch (the index_select of the states and
+ * ctc_state[j] / ctc_prob[j] of asr.py:240-245).  For each new slot r = u*beam + s, s < n_new[u], step < limit[u],
+ * with p = u*beam + parent[r] and j = j_new[r]:
+ *   hs/cs [NL][2][R][C]: slot 0 of row r <- slot 1 of row p;  att [2][R][Tmax]: att[0][r] <- att[1][p] (NULL: skipped)
+ *   r_prev [R][Tmax][2] <- r_out [R][K][Tmax][2] at (p, j), frames t < T_u[u];  prev_ctc [R] <- psi [R][K] at (p, j)
+ *   (r_out NULL: no CTC state);  tok / plen / sum [R] <- tok_new / plen_new / sum_new;  n_live[u] <- n_new[u].
+ * Source and destination are different buffers (or different slots of one): nothing is gathered in place. */
+int las_beam_gather(int U, int beam, int NL, int C, int Tmax, int K, const int32_t* T_u, const int32_t* limit, int step,
+                    const int32_t* n_new, const int32_t* parent, const int32_t* j_new, const int32_t* tok_new,
+                    const int32_t* plen_new, const double* sum_new, float* hs, float* cs, float* att,
+                    const float* r_out, const float* psi, float* r_prev, float* prev_ctc, int32_t* tok, int32_t* plen,
+                    double* sum, int32_t* n_live, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

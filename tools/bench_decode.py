@@ -1,5 +1,8 @@
 """Decode-path measurement (N3): beam search of one utterance through Seq2Seq.beam_decode on the GPU vs the CPU oracle's
-restatement of the reference's per-hypothesis loop.  Usage: python tools/bench_decode.py [--beam 20] [--V 31] [--cpu]"""
+restatement of the reference's per-hypothesis loop.  Usage: python tools/bench_decode.py [--beam 20] [--V 31] [--cpu]
+--batch U[,U2..]: the batched, device-resident path (Seq2Seq.beam_decode_batch) against the one-utterance path, the two run
+alternately in one process over the same --utts utterances for --rounds rounds; reports the median and the run-to-run
+spread (min..max over rounds) of each.  --only-batch N: nothing but N batched calls after a warm-up (for profiler runs)."""
 import argparse, importlib, json, os, sys, time
 import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
@@ -14,6 +17,10 @@ def main():
     ap.add_argument('--utts', type=int, default=5)
     ap.add_argument('--cpu', action='store_true', help='also time the CPU oracle (bounded: --cpu-steps decode steps)')
     ap.add_argument('--cpu-steps', type=int, default=10)
+    ap.add_argument('--batch', type=str, default='', help='comma-separated batch sizes of the batched path to time')
+    ap.add_argument('--rounds', type=int, default=3)
+    ap.add_argument('--only-batch', type=int, default=0)
+    ap.add_argument('--out', type=str, default='')
     a = ap.parse_args()
     importlib.import_module('end-to-end-asr-pytorch_amd')
     ops = importlib.import_module('end-to-end-asr-pytorch_amd.ops')
@@ -32,6 +39,8 @@ def main():
     model.eval()
     steps = int(a.T * a.ratio)
     xd = x.cuda()
+    if a.batch:
+        return batch_main(a, model, steps, cfg)
     model.beam_decode(xd, steps, [a.T], a.beam)                    # warm-up
     torch.cuda.synchronize()
     t0 = time.time()
@@ -54,6 +63,65 @@ def main():
         out.update(cpu_oracle_s_for_steps=dc, cpu_steps=a.cpu_steps, cpu_ms_per_decode_step=1e3 * dc / a.cpu_steps,
                    note='CPU time includes one encoder pass; the oracle restates the reference\'s per-hypothesis numpy/torch loop')
     print(json.dumps(out))
+
+
+def batch_main(a, model, steps, cfg):
+    """One-utterance path (unchanged code) vs batched path, alternately; every shape is warmed before it is timed."""
+    sizes = [int(v) for v in a.batch.split(',')]
+    g = torch.Generator().manual_seed(1)
+    xs = torch.randn(a.utts, a.T, 80, generator=g).cuda()
+    lens = [a.T] * a.utts
+
+    def single():
+        for u in range(a.utts):
+            model.beam_decode(xs[u:u + 1], steps, [a.T], a.beam)
+
+    def batched(U):
+        for b in range(0, a.utts, U):
+            model.beam_decode_batch(xs[b:b + U], steps, lens[b:b + U], a.beam)
+
+    def timed(fn, *args):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn(*args)
+        torch.cuda.synchronize()                       # (both paths end in a D2H read; this closes the interval regardless)
+        return (time.perf_counter() - t0) / a.utts
+
+    if a.only_batch:
+        batched(sizes[0])                              # warm-up
+        torch.cuda.synchronize()
+        for _ in range(a.only_batch):
+            batched(sizes[0])
+        torch.cuda.synchronize()
+        print(json.dumps(dict(only_batch=a.only_batch, U=sizes[0], utts=a.utts, decode_steps=steps)))
+        return
+    single()
+    for U in sizes:
+        batched(U)
+    assert int(model.status.item()) == 0
+    rec = {'single': []}
+    rec.update({U: [] for U in sizes})
+    for _ in range(a.rounds):
+        rec['single'].append(timed(single))
+        for U in sizes:
+            rec[U].append(timed(batched, U))
+    assert int(model.status.item()) == 0
+
+    def summary(v):
+        v = sorted(v)
+        med = v[len(v) // 2]
+        return dict(gpu_s_per_utt=med, gpu_ms_per_decode_step=1e3 * med / steps, utts_per_s=1.0 / med,
+                    spread_s_per_utt=[v[0], v[-1]], rounds_s_per_utt=v)
+    out = dict(workload=f'beam decode, 5x320 pBLSTM loc-attn + CTC 0.5, T={a.T} (T\'={a.T // 4}), V={a.V}, beam={a.beam}, '
+                        f'{steps} decode steps, bf16, {a.utts} utterances per pass, {a.rounds} alternating rounds',
+               protocol='host clock around a pass over all utterances ending in a device synchronise; per round: one-utterance '
+                        'path, then each batch size; every shape warmed first; median over rounds, spread = min..max',
+               one_utterance_path=summary(rec['single']),
+               batched={f'U={U}': summary(rec[U]) for U in sizes})
+    print(json.dumps(out))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        json.dump(out, open(a.out, 'w'), indent=1)
 
 
 if __name__ == '__main__':

@@ -1693,6 +1693,7 @@ __global__ __launch_bounds__(NT + 64) void lstm_bwd_gr_kernel(LstmArgs a, const 
     GR_ST_PRINT(a.T);
 }
 #include "lstm_x32.h"
+#include "lstm_f32w.h"
 
 size_t bwd_gr_lds(int H, int NB) {
     const int G = (H + 15) / 16, mt = (G + 3) / 4, PS = mt <= 5 ? 20 : mt <= 8 ? 32 : 64, RLD = 16 * PS + 4;
@@ -1834,8 +1835,22 @@ int launch_bwd(const LstmArgs& a, int NC, int K4p, size_t lds, hipStream_t st, c
 
 
 // Which backward kernel a shape gets, its LDS request and the size of its exchange workspace (`dgx`).
-struct BwdPlan { bool ks, wdirect, gr; int NB, NC, K4p; size_t lds, ws; };
+struct BwdPlan { bool ks, wdirect, gr, f32w; int NB, NC, K4p; size_t lds, ws; };
+int bwd_plan_lds(int prec, int T, int B, int H, int ND, const LstmArgs& a, BwdPlan& p);
 int bwd_plan(int prec, int T, int B, int H, int ND, const LstmArgs& a, BwdPlan& p) {
+    p.f32w = false;
+    const int rc = bwd_plan_lds(prec, T, B, H, ND, a, p);
+    // fp32 mode, no LDS placement of W_hh fits: the K-split kernel with its weight fragments in registers (lstm_f32w.h)
+    if (rc != LAS_E_UNSUPPORTED || !f32w_ok(prec, H, p.NB) || ND * ((H + 15) / 16) > las_cu_count() ||
+        bwd_f32w_lds(H, p.NB) > LDS_CAP) return rc;
+    p.ks = p.f32w = true; p.wdirect = p.gr = false;
+    p.NC = 1; p.K4p = 4 * H;
+    p.lds = bwd_f32w_lds(H, p.NB);
+    p.ws = bwd_ks_ring_bytes(prec, H, ND, a.NS, p.NB);
+    if (p.lds < MIN_LDS) p.lds = MIN_LDS;
+    return LAS_OK;
+}
+int bwd_plan_lds(int prec, int T, int B, int H, int ND, const LstmArgs& a, BwdPlan& p) {
     p.NB = las_pick_nb(a.Bs);
     if (p.NB == 0 || ND * ((H + 15) / 16) > las_cu_count()) return LAS_E_UNSUPPORTED;
     // K-split exchange (reduce-scatter of partial dh) whenever it fits: the [H][64] weight slab in LDS, or (bf16) the
@@ -2022,7 +2037,32 @@ static int rec_fwd_impl(int prec, const float* xproj, const float* b_ih, const f
     }
     if (prec == LAS_PREC_BF16 && NB <= 2 && KS == 0 && ksteps <= 32 && fwd_lds(prec, H, NB, false) > LDS_CAP) KS = 32;
     size_t lds = fwd_lds(prec, H, NB, KS > 0);
-    if (lds > LDS_CAP) return LAS_E_UNSUPPORTED;
+    if (lds > LDS_CAP) {
+        // fp32 mode: the W_hh slab does not fit LDS -> weight fragments in registers (lstm_f32w.h), 16-unit workgroups
+        if (fxI > 0 || prec != LAS_PREC_F32) return LAS_E_UNSUPPORTED;
+        if (U != 16) fill_args(a, T, B, H, ND, 16, sr, concat);
+        if (!f32w_ok(prec, H, las_pick_nb(a.Bs)) || fwd_f32w_lds(H, las_pick_nb(a.Bs)) > LDS_CAP) return LAS_E_UNSUPPORTED;
+        a.y_is_hf = (y == hf);
+        a.tw = tw;
+        if (a.y_is_hf && sr != 1) return LAS_E_BADARG;
+        lds = fwd_f32w_lds(H, las_pick_nb(a.Bs));
+        if (lds < MIN_LDS) lds = MIN_LDS;
+        hipStream_t st = (hipStream_t)stream;
+        LAS_HIP(hipMemsetAsync(sync, 0, sizeof(SyncWords), st));
+#define LAS_F32W_FWD(N_, K_)                                                                                            \
+    {                                                                                                                 \
+        auto k = lstm_fwd_f32w_kernel<N_, K_>;                                                                        \
+        LAS_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));           \
+        hipLaunchKernelGGL(k, dim3(lstm_grid(a)), dim3(NT), lds, st, a, xproj, b_ih, b_hh, w_hh, lens, y, hf, (float*)hx, \
+                           gates, cs, (SyncWords*)sync, status);                                                      \
+        LAS_LAUNCH_OK();                                                                                              \
+        return LAS_OK;                                                                                                \
+    }
+        const int ks16 = (H + 15) / 16;
+        if (las_pick_nb(a.Bs) == 1) { if (ks16 <= 32) LAS_F32W_FWD(1, 32) else if (ks16 <= 48) LAS_F32W_FWD(1, 48) else LAS_F32W_FWD(1, 64) }
+        else { if (ks16 <= 32) LAS_F32W_FWD(2, 32) else if (ks16 <= 48) LAS_F32W_FWD(2, 48) else LAS_F32W_FWD(2, 64) }
+#undef LAS_F32W_FWD
+    }
     a.y_is_hf = (y == hf);
     a.tw = tw;
     if (a.y_is_hf && sr != 1) return LAS_E_BADARG;
@@ -2162,6 +2202,21 @@ static int rec_bwd_impl(int prec, const float* dy, const float* gates, const flo
         if (NB == 1) { if (mt <= 5) LAS_GR_GO(1, 5) else if (mt <= 8) LAS_GR_GO(1, 8) else LAS_GR_GO(1, 16) }
         else { if (mt <= 5) LAS_GR_GO(2, 5) else LAS_GR_GO(2, 8) }
 #undef LAS_GR_GO
+    }
+    if (p.f32w) {
+#define LAS_F32W_BWD(N_, M_)                                                                                            \
+    {                                                                                                                 \
+        auto k = lstm_bwd_f32w_kernel<N_, M_>;                                                                        \
+        LAS_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));           \
+        hipLaunchKernelGGL(k, dim3(lstm_grid(a)), dim3(NT), lds, st, a, dy, gates, cs, w_hh, lens, (unsigned*)dgx, dgf, \
+                           (SyncWords*)sync, status);                                                                 \
+        LAS_LAUNCH_OK();                                                                                              \
+        return LAS_OK;                                                                                                \
+    }
+        const int mt = (a.G + 3) / 4;
+        if (NB == 1) { if (mt <= 8) LAS_F32W_BWD(1, 8) else if (mt <= 12) LAS_F32W_BWD(1, 12) else LAS_F32W_BWD(1, 16) }
+        else { if (mt <= 8) LAS_F32W_BWD(2, 8) else if (mt <= 12) LAS_F32W_BWD(2, 12) else LAS_F32W_BWD(2, 16) }
+#undef LAS_F32W_BWD
     }
     if (p.ks) {
 #define LAS_KS_GO(P_, N_, M_)                                                                                          \

@@ -1,13 +1,15 @@
 """Sweep of the persistent LSTM kernels' time per dependent timestep over H (workgroups per direction = H/16) and B
-(batch slices of <= 12 rows): what does the hand-off cost depend on?  Kernel-only (HIP events around the C call)."""
+(batch slices of <= 12 rows): what does the hand-off cost depend on?  Kernel-only (HIP events around the C call).
+Environment: PREC = bf16 (default) | f32, T, SR, ONLY_H."""
 import importlib, sys
 import torch
 sys.path.insert(0, '.')
 importlib.import_module('end-to-end-asr-pytorch_amd')
 ops = importlib.import_module('end-to-end-asr-pytorch_amd.ops')
 dev = 'cuda:0'
-ops.set_precision('bf16')
 import os
+PREC = os.environ.get('PREC', 'bf16')
+ops.set_precision(PREC)
 T = int(os.environ.get("T", 300))
 SR = int(os.environ.get("SR", 1))
 SHAPES = [(24, 320, 2), (12, 320, 2), (12, 320, 1), (24, 160, 2), (12, 160, 2), (12, 64, 2), (12, 32, 1), (12, 16, 1), (48, 320, 2), (24, 512, 2), (24, 1024, 2), (12, 1024, 2), (24, 768, 2)]
@@ -34,4 +36,4 @@ for (B, H, ND) in SHAPES:
     fw = [e0.elapsed_time(e1) for n, e0, e1, *_ in rec if n.startswith('lstm_fwd')]
     bw = [e0.elapsed_time(e1) for n, e0, e1, *_ in rec if n.startswith('lstm_bwd')]
     ops.disable_kernel_timing()
-    print(f'B={B:3d} H={H:4d} ND={ND} WGs/dir={H // 16:3d} slices={(B + 11) // 12}: fwd {min(fw) * 1e3 / T:.2f} us/step  bwd {min(bw) * 1e3 / T:.2f} us/step  status={status.item()}', flush=True)
+    print(f'{PREC} B={B:3d} H={H:4d} ND={ND} WGs/dir={H // 16:3d} slices={(B + 11) // 12}: fwd {min(fw) * 1e3 / T:.2f} us/step  bwd {min(bw) * 1e3 / T:.2f} us/step  status={status.item()}', flush=True)

@@ -127,6 +127,28 @@ class LibriBuckets(_Buckets):
         return _pad_x(xs), _pad_y([l for _, _, l in items])
 
 
+def label_prior(train_set, V):
+    """Unigram distribution of the training labels, float32 [V]: every non-zero token at positions >= 1 of every label row
+    (position 0 is <sos>, which is never a target), counted over the WHOLE buckets -- before the rank shard, so every rank
+    gets the same vector -- and normalised to sum 1; class 0 (padding / <sos>, the ignored target) gets 0.  The synthetic
+    source draws new labels every epoch and has no such distribution: ValueError."""
+    if not isinstance(train_set, _Buckets):
+        raise ValueError('a unigram label prior needs a stored training set (TIMIT / LibriSpeech), not the %s source'
+                         % type(train_set).__name__)
+    counts = np.zeros(int(V), np.int64)
+    for item in train_set.items:
+        rows = item[1] if isinstance(train_set, TimitBuckets) else [l for _, _, l in item]
+        for row in rows:
+            tok = np.asarray(row, np.int64)[1:]
+            tok = tok[tok != 0]
+            if tok.size and (tok.min() < 0 or tok.max() >= V):
+                raise ValueError('training label outside [0, %d)' % V)
+            counts += np.bincount(tok, minlength=int(V))
+    if counts.sum() == 0:
+        raise ValueError('the training set has no labels to count')
+    return (counts / counts.sum()).astype(np.float32)
+
+
 def LoadDataset(split, text_only, data_path, batch_size, max_timestep, max_label_len, use_gpu, n_jobs, dataset,
                 train_set, dev_set, test_set, dev_batch_size, decode_beam_size, **kwargs):
     """Same signature as reference dataset.py:119 (extra YAML keys are swallowed)."""

@@ -736,11 +736,14 @@ def lstm_layer_leaves(x, lens, cats, sr, concat, status, ND, leaves, cat_grads=N
 # ----------------------------------------------------------------------------- joint loss
 class JointLossFn(torch.autograd.Function):
     """asr_loss = (1-w)*att_loss + w*ctc_loss, reference solver.py:144-164.
-    forward(att_pred [B,L,V]|None, ctc_pred [B,T',V]|None, y i64 [B,Ly], ntok i32 [B], enc_len i32 [B], L, w)
-      -> (asr_loss, att_loss, ctc_loss) 0-dim tensors (att/ctc are non-differentiable by-products)."""
+    forward(att_pred [B,L,V]|None, ctc_pred [B,T',V]|None, y i64 [B,Ly], ntok i32 [B], enc_len i32 [B], L, w,
+            label_smoothing=0.0, prior=None)
+      -> (asr_loss, att_loss, ctc_loss) 0-dim tensors (att/ctc are non-differentiable by-products).
+    label_smoothing > 0 or a prior (fp32 [V], checked by joint_loss) smooths the attention targets (las_ce_loss_ls, not in
+    the reference); without either the call is the reference's plain loss through las_ce_loss."""
 
     @staticmethod
-    def forward(ctx, att_pred, ctc_pred, y, ntok, enc_len, L, w):
+    def forward(ctx, att_pred, ctc_pred, y, ntok, enc_len, L, w, label_smoothing=0.0, prior=None):
         L_ = _lib.lib()
         ctx.set_materialize_grads(False)         # (att_loss / ctc_loss are by-products: no zero fills for their gradients)
         dev = y.device
@@ -753,8 +756,15 @@ class JointLossFn(torch.autograd.Function):
             att = torch.empty(1, **f32)
             datt = torch.empty_like(att_pred)
             rowloss = torch.empty(B * Lx, **f32)
-            check(L_.las_ce_loss(ptr(att_pred), ptr(y), I(y.shape[1]), ptr(ntok), I(B), I(Lx), I(V), F(1.0 - w),
-                                 ptr(rowloss), ptr(att), ptr(datt), cur_stream()), 'las_ce_loss')
+            if label_smoothing > 0 or prior is not None:
+                if prior is not None and prior.numel() != V:
+                    raise ValueError(f'label-smoothing prior has {prior.numel()} entries, the logits have V = {V}')
+                check(L_.las_ce_loss_ls(ptr(att_pred), ptr(y), I(y.shape[1]), ptr(ntok), I(B), I(Lx), I(V), F(1.0 - w),
+                                        F(label_smoothing), ptr(prior), ptr(rowloss), ptr(att), ptr(datt), cur_stream()),
+                      'las_ce_loss_ls')
+            else:
+                check(L_.las_ce_loss(ptr(att_pred), ptr(y), I(y.shape[1]), ptr(ntok), I(B), I(Lx), I(V), F(1.0 - w),
+                                     ptr(rowloss), ptr(att), ptr(datt), cur_stream()), 'las_ce_loss')
         cs = getattr(ctc_pred, '_branch', None) if ctc_pred is not None else None
         pend, _BRANCH['pending'] = _BRANCH.get('pending'), None
         if cs is None and pend is not None:
@@ -803,7 +813,7 @@ class JointLossFn(torch.autograd.Function):
     def backward(ctx, g, _ga, _gc):
         L_ = _lib.lib()
         if g is None:
-            return None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None, None
         g = g.contiguous().view(1).float()
         gatt = gctc = None
         if ctx.ctc is not None:
@@ -822,11 +832,39 @@ class JointLossFn(torch.autograd.Function):
             gatt = ctx.datt
             check(L_.las_scale_dev(ptr(gatt), LL(gatt.numel()), ptr(g), cur_stream()), 'las_scale_dev')
         ctx.datt = ctx.ctc = None
-        return gatt, gctc, None, None, None, None, None
+        return gatt, gctc, None, None, None, None, None, None, None
 
 
-def joint_loss(att_pred, ctc_pred, y, ntok, enc_len, L, w):
-    return JointLossFn.apply(att_pred, ctc_pred, y, ntok, enc_len, L, float(w))
+def check_prior(prior, V=None):
+    """A label-smoothing prior is an fp32 device vector [V], non-negative, summing to 1 within 1e-4; ValueError otherwise.
+    The check reads two scalars back, so a tensor that passed is remembered (until it is written to in place)."""
+    if not isinstance(prior, torch.Tensor) or prior.dtype != torch.float32 or prior.dim() != 1:
+        raise ValueError('label-smoothing prior must be a 1-D fp32 tensor [V]')
+    if not prior.is_cuda or not prior.is_contiguous():
+        raise ValueError('label-smoothing prior must be a contiguous HIP device tensor')
+    if V is not None and prior.numel() != V:
+        raise ValueError(f'label-smoothing prior has {prior.numel()} entries, the logits have V = {V}')
+    if getattr(prior, '_las_prior_ok', None) == prior._version:
+        return prior
+    lo, tot = torch.stack([prior.min(), prior.double().sum().float()]).tolist()
+    if not lo >= 0.0:
+        raise ValueError(f'label-smoothing prior has a negative (or NaN) entry: min {lo}')
+    if not abs(tot - 1.0) <= 1e-4:
+        raise ValueError(f'label-smoothing prior sums to {tot}, not 1')
+    prior._las_prior_ok = prior._version
+    return prior
+
+
+def joint_loss(att_pred, ctc_pred, y, ntok, enc_len, L, w, label_smoothing=0.0, prior=None):
+    """label_smoothing in [0, 1) and `prior` (fp32 device tensor [V]; None = uniform) smooth the attention targets:
+    t = (1 - eps) * onehot + eps * prior, torch's F.cross_entropy(label_smoothing=eps) for the uniform prior.  With neither,
+    the call is the reference's plain loss, bit for bit what it was before the option existed."""
+    label_smoothing = float(label_smoothing)
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(f'label_smoothing must be in [0, 1), got {label_smoothing}')
+    if prior is not None:
+        check_prior(prior, att_pred.shape[-1] if att_pred is not None else None)
+    return JointLossFn.apply(att_pred, ctc_pred, y, ntok, enc_len, L, float(w), label_smoothing, prior)
 
 
 # ----------------------------------------------------------------------------- metrics

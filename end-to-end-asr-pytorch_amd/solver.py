@@ -15,13 +15,33 @@ import torch
 
 from . import ops, dist as ldist
 from .asr import Seq2Seq
-from .dataset import LoadDataset
+from .dataset import LoadDataset, label_prior
 from .optim import FlatOptimizer
 from .postprocess import Mapper, cal_acc, cal_cer, draw_att
 
 VAL_STEP = 30            # reference solver.py:18-20
 TRAIN_WER_STEP = 250
 GRAD_CLIP = 5
+
+
+def label_smoothing_config(config):
+    """asr_model.optimizer.label_smoothing (float in [0, 1), default 0) and .label_smoothing_prior ('uniform', the default,
+    or 'unigram': the training labels' distribution, dataset.label_prior) -> (eps, prior kind); ValueError for anything else.
+    Not in the reference, whose attention loss is never smoothed."""
+    opt = config['asr_model']['optimizer']
+    try:
+        eps = float(opt.get('label_smoothing', 0.0))
+    except (TypeError, ValueError):
+        raise ValueError('label_smoothing must be a number in [0, 1), got %r' % (opt.get('label_smoothing'),))
+    if not 0.0 <= eps < 1.0:
+        raise ValueError('label_smoothing must be in [0, 1), got %r' % (opt.get('label_smoothing'),))
+    kind = str(opt.get('label_smoothing_prior', 'uniform')).lower()
+    if kind not in ('uniform', 'unigram'):
+        raise ValueError("label_smoothing_prior must be 'uniform' or 'unigram', got %r" % (opt.get('label_smoothing_prior'),))
+    if kind == 'unigram' and str(config['solver'].get('dataset', '')).upper() == 'SYNTHETIC':
+        raise ValueError("label_smoothing_prior 'unigram' needs a stored training set: the synthetic source draws new labels "
+                         'every epoch')
+    return eps, kind
 
 
 class ScalarLog:
@@ -108,6 +128,8 @@ class Trainer(Solver):
         if config.get('clm', {}).get('enable', False):
             raise NotImplementedError('CLM adversarial training is out of scope (SURVEY.md §2.1)')
         self._pending = None
+        self.label_smoothing, self.ls_prior_kind = label_smoothing_config(config)
+        self.ls_prior = None             # device fp32 [V] for 'unigram' (set_model); None = uniform
         self.len_stream = True           # length inference + its D2H on a stream of their own (train_step; tests switch it off)
 
     # ------------------------------------------------------------------------------------------------ data
@@ -129,6 +151,9 @@ class Trainer(Solver):
         mp = self.config['asr_model']
         self.asr_model = Seq2Seq(self.sample_x, self.mapper.get_dim(), mp, device=self.device)
         self.ctc_weight = mp['optimizer']['joint_ctc']
+        if self.label_smoothing > 0 and self.ls_prior_kind == 'unigram':      # counted over the whole buckets: the same on every rank
+            self.ls_prior = torch.from_numpy(label_prior(self.train_set, self.mapper.get_dim())).to(self.device)
+            ops.check_prior(self.ls_prior, self.mapper.get_dim())             # (its read-back happens here, not in the first step)
         self.asr_opt = FlatOptimizer(self.asr_model, mp['optimizer']['type'], mp['optimizer']['learning_rate'], eps=1e-8,
                                      world_size=self.world)
         if self.paras.load:
@@ -189,8 +214,9 @@ class Trainer(Solver):
                                                              state_len_dev=lens)
         finally:
             self.asr_model.ctc_branch = False
+        # (label smoothing is a training regulariser: valid() keeps the plain loss, so dev losses stay comparable between runs)
         loss, att_loss, ctc_loss = ops.joint_loss(att_pred, ctc_pred, y, ntok, self.asr_model.last_enc_len_dev, ans_len,
-                                                  self.ctc_weight)
+                                                  self.ctc_weight, label_smoothing=self.label_smoothing, prior=self.ls_prior)
         ldist.backward_with_overlap(loss if shard_weight == 1.0 else loss * shard_weight, self.asr_model)   # solver.py:177
         self.asr_opt.step(zero_grad=True)                         # clip 5, NaN guard, update (solver.py:178-182)
         return loss, att_loss, ctc_loss, att_pred, ans_len

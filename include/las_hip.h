@@ -259,6 +259,17 @@ int las_transpose2d(const float* in, float* out, int R, int C, void* stream);
  * dlogits = gscale * d loss / d logits (pass NULL to skip).  rowloss [B*L] scratch, loss [1]. */
 int las_ce_loss(const float* logits, const int64_t* y, int Ly, const int32_t* ntok, int B, int L, int V, float gscale,
                 float* rowloss, float* loss, float* dlogits, void* stream);
+/* The same loss with label smoothing (NOT in the reference: its call site src/solver.py:90,149-155 builds the plain
+ * CrossEntropyLoss above; this is what that line would compute with label_smoothing=eps).  Target of a row:
+ * t_v = (1-eps)*[v == label] + eps*q_v, q = prior [V] (a distribution, e.g. the training set's unigram) or 1/V for every
+ * class when prior is NULL -- the definition of torch.nn.functional.cross_entropy(label_smoothing=eps).
+ *   rowloss = lse - (1-eps)*x[label] - eps*sum_v q_v*x_v,   dlogits_v = w*(softmax_v - t_v),  w = gscale/(B*max(ntok_b,1)).
+ * Everything else is las_ce_loss's contract: label = y[b][t+1]; rows with label 0, < 0 or >= V are ignored (rowloss 0,
+ * zero gradient row); every output element is written; no workspace.  eps outside [0,1) -> LAS_E_BADARG.
+ * V <= 1024: one wave per row, the row held in registers; V > 1024: one workgroup per row, online softmax. */
+int las_ce_loss_ls(const float* logits, const int64_t* y, int Ly, const int32_t* ntok, int B, int L, int V, float gscale,
+                   float eps, const float* prior /* [V], NULL = uniform 1/V */,
+                   float* rowloss, float* loss, float* dlogits /* may be NULL */, void* stream);
 /* CTCLoss reduction='mean': out[0] = mean_b x[b]/max(n[b],1) (src/solver.py:93,160) and its gradient
  * gx[b] = g[0]*scale/(B*max(n[b],1)). */
 int las_norm_mean_fwd(const float* x, const int32_t* n, int B, float* out, void* stream);

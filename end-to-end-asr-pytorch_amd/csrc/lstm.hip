@@ -24,6 +24,7 @@
 // Backward mirrors this with dgates[B,4H] as the exchanged quantity and W_hh^T columns resident.
 #include <type_traits>
 #include "las_mma.h"
+#include <stdio.h>
 #include <stdlib.h>
 
 namespace {
@@ -1727,14 +1728,15 @@ size_t bwd_lds(int prec, int H, int NB, int NC) {
     return (size_t)16 * (K4p + vec) * sz + (size_t)NB * 16 * (KC + vec) * sz + sizeof(float) * 4 * NB * 16 * 17 +
            sizeof(int) * (NB * 16 + 4);
 }
-constexpr size_t LDS_CAP = 160 * 1024;
-
-
-int check_common(int T, int B, int H, int ND, int sr) {
-    if (T <= 0 || B <= 0 || H <= 0 || (ND != 1 && ND != 2) || sr < 1) return LAS_E_BADARG;
-    if (H % 2 != 0) return LAS_E_UNSUPPORTED;          // pair stores / float2 accesses
-    return LAS_OK;
+size_t fwd_gr_lds(int H, int NB, int swm = 4) {
+    const int Kp = (H + 31) / 32 * 32, ld = Kp + 16;
+    return (size_t)2 * NB * 16 * ld * 2 + sizeof(float) * 2 * NB * 16 * (2 * GR_XLD + GR_HLD) + sizeof(int) * (NB * 16 + 4) +
+           (swm > 4 ? sizeof(int) * NT * swm * 2 : 0);
 }
+size_t fwd_gr_ring_bytes(const LstmArgs& a) {
+    return (size_t)16 * a.ND * HX_SLOTS * a.NS * a.H * ((a.Bs >> 4) * 3 + ((a.Bs & 15) + 5) / 6);
+}
+constexpr size_t LDS_CAP = 160 * 1024;
 
 void fill_args(LstmArgs& a, int T, int B, int H, int ND, int U, int sr, int concat, int force_ns = 0) {
     a.T = T; a.B = B; a.H = H; a.ND = ND; a.U = U; a.G = (H + U - 1) / U;
@@ -1768,125 +1770,321 @@ void fill_args(LstmArgs& a, int T, int B, int H, int ND, int U, int sr, int conc
     a.pdelay = pd ? atoi(pd) : 0;
 }
 int lstm_grid(const LstmArgs& a) { return a.xl ? 8 * a.G * ((a.ND * a.NS + 7) / 8) : a.ND * a.G * a.NS; }
-
-// The 32-unit geometry (lstm_x32.h): bf16, 512 < H <= 1024, slices of <= 16 rows, every group on an XCD of its own.
 inline int host_gr_chunks(int rows) { return (rows >> 4) * 3 + ((rows & 15) + 5) / 6; }
-bool use_x32(int prec, int T, int B, int H, int ND, int sr, int concat, LstmArgs& a) {
-    if (prec != LAS_PREC_BF16 || H <= 512 || H > 1024 || (H & 3)) return false;
-    if (las_fallback("LAS_LSTM_NO_GR") || las_fallback("LAS_LSTM_NO_XL") || las_fallback("LAS_LSTM_NO_X32")) return false;
-    // slices of >= 6 rows while every (direction, slice) group still gets an XCD of its own: the sweeps shrink with the
-    // slice (C5, B = 24: four slices of 6 instead of two of 12: forward 3.7 -> 3.1, backward 6.1 -> 4.8 us per step, C5 step
-    // 55.3 -> 48.6 ms), at the price of occupying all eight XCDs
-    int ns = (B + 5) / 6;
-    if (ns > 8 / ND) ns = 8 / ND;
-    if (ns < (B + 15) / 16) ns = (B + 15) / 16;
-    if (const char* e = LAS_AB_KNOB("LAS_LSTM_X32_NS")) ns = atoi(e);      // (diagnostic build: force the slice count)
-    fill_args(a, T, B, H, ND, 32, sr, concat, ns);
-    if (!a.xl || a.Bs > 16 || a.NS > MAX_SLICES || ND * a.NS > 8) return false;
-    if ((long)T * B * ND * 4 * H * 4 >= (1l << 31)) return false;
-    if ((long)H * host_gr_chunks(a.Bs) > 8 * 256 || (long)a.G * a.Bs * 8 > X32_SWB * 256) return false;
-    return true;
+
+// The first stage of both plans: the argument check, then the geometry.  *x32: the 32-unit geometry (lstm_x32.h): bf16,
+// 512 < H <= 1024, slices of <= 16 rows, every group on an XCD of its own; otherwise `a` holds the 16-unit geometry.
+int plan_args(int prec, int T, int B, int H, int ND, int sr, int concat, LstmArgs& a, bool* x32) {
+    *x32 = false;
+    if (T <= 0 || B <= 0 || H <= 0 || (ND != 1 && ND != 2) || sr < 1) return LAS_E_BADARG;
+    if (H % 2 != 0) return LAS_E_UNSUPPORTED;          // pair stores / float2 accesses
+    if (prec == LAS_PREC_BF16 && H > 512 && H <= 1024 && !(H & 3) && !las_fallback("LAS_LSTM_NO_GR") &&
+        !las_fallback("LAS_LSTM_NO_XL") && !las_fallback("LAS_LSTM_NO_X32")) {
+        // slices of >= 6 rows while every (direction, slice) group still gets an XCD of its own: the sweeps shrink with the
+        // slice (C5, B = 24: four slices of 6 instead of two of 12: forward 3.7 -> 3.1, backward 6.1 -> 4.8 us per step, C5 step
+        // 55.3 -> 48.6 ms), at the price of occupying all eight XCDs
+        int ns = (B + 5) / 6;
+        if (ns > 8 / ND) ns = 8 / ND;
+        if (ns < (B + 15) / 16) ns = (B + 15) / 16;
+        if (const char* e = LAS_AB_KNOB("LAS_LSTM_X32_NS")) ns = atoi(e);      // (diagnostic build: force the slice count)
+        fill_args(a, T, B, H, ND, 32, sr, concat, ns);
+        *x32 = a.xl && a.Bs <= 16 && a.NS <= MAX_SLICES && ND * a.NS <= 8 && (long)T * B * ND * 4 * H * 4 < (1l << 31) &&
+               (long)H * host_gr_chunks(a.Bs) <= 8 * 256 && (long)a.G * a.Bs * 8 <= X32_SWB * 256;
+        if (*x32) return LAS_OK;
+    }
+    fill_args(a, T, B, H, ND, 16, sr, concat);
+    return LAS_OK;
 }
 
-template <int PREC, int NB, int KS>
-int launch_fwd(const LstmArgs& a, size_t lds, hipStream_t st, const float* xproj, const float* b_ih, const float* b_hh,
-               const float* w_hh, const int32_t* lens, float* y, float* hf, void* hx, float* gates, float* cs,
-               SyncWords* sync, int* status) {
-    auto k = lstm_fwd_kernel<PREC, NB, KS>;
-    LAS_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+// ------------------------------------------------------------------------------------------------ plan and instance table
+// What a launch passes behind LstmArgs.  The kernels type their exchange buffer differently (CT<PREC>::T*, float*, unsigned*,
+// u32x4*): ExPtr converts to whichever the selected instance declares.
+struct ExPtr {
+    void* p;
+    template <typename T> operator T*() const { return (T*)p; }
+};
+struct FwdIo {
+    const float *xproj, *b_ih, *b_hh, *w_hh;
+    const int32_t* lens;
+    float *y, *hf;
+    ExPtr hx;
+    float *gates, *cs;
+    SyncWords* sync;
+    int* status;
+};
+struct BwdIo {
+    const float *dy, *gates, *cs, *w_hh;
+    const int32_t* lens;
+    ExPtr dgx;
+    float* dgf;
+    SyncWords* sync;
+    int* status;
+};
+
+enum Kernel { K_lstm_fwd_kernel, K_lstm_fwd_gr_kernel, K_lstm_fwd_x32_kernel, K_lstm_fwd_f32w_kernel, K_lstm_bwd_kernel,
+              K_lstm_bwd_ks_kernel, K_lstm_bwd_gr_kernel, K_lstm_bwd_x32_kernel, K_lstm_bwd_f32w_kernel };
+// The int codes of las_lstm_fwd_variant / las_lstm_bwd_is_ksplit (the f32w kernels report as the family they stand in for).
+int variant_code(int kernel) {
+    switch (kernel) {
+        case K_lstm_fwd_gr_kernel: case K_lstm_bwd_ks_kernel: case K_lstm_bwd_f32w_kernel: return 1;
+        case K_lstm_fwd_x32_kernel: case K_lstm_bwd_gr_kernel: return 2;
+        case K_lstm_bwd_x32_kernel: return 3;
+        default: return 0;
+    }
+}
+
+template <typename Io> struct Plan;
+template <typename Io> struct Row {       // one kernel instance the dispatch can launch
+    int (*launch)(const Plan<Io>&, const Io&, hipStream_t);
+    const char* name;
+    int kernel, targ[4];                  // family and template arguments: what the plan selects by
+};
+// Everything the choice of kernel determines for one shape: computed afresh by plan_fwd / plan_bwd on every call (the
+// las_fallback switches are read per launch), read by the launches and by every size / variant query.
+template <typename Io> struct Plan {
+    int rc;                     // LAS_OK and a row, or what the launch returns instead
+    LstmArgs a;
+    const Row<Io>* row;
+    int grid, block;
+    size_t lds;                 // dynamic LDS request
+    size_t fill;                // bytes of the exchange ring the launch zero-fills (tags of earlier launches must not match); 0: none
+    size_t ws;                  // bytes of exchange workspace (hx / dgx) the caller provides
+    bool twin;                  // the kernel writes the bf16 twin (LstmArgs::tw) itself
+    int NC, K4p;                // all-gather backward: column chunks and padded width of the d gates copy
+};
+typedef Plan<FwdIo> FwdPlan;
+typedef Plan<BwdIo> BwdPlan;
+
+template <typename... A> constexpr int kernel_arity(void (*)(A...)) { return sizeof...(A); }
+template <auto K, typename Io>
+int launch(const Plan<Io>& p, const Io& io, hipStream_t st) {
+    LAS_HIP(hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+    const dim3 grid(p.grid), block(p.block);
+    if constexpr (std::is_same<Io, FwdIo>::value)
+        hipLaunchKernelGGL(K, grid, block, p.lds, st, p.a, io.xproj, io.b_ih, io.b_hh, io.w_hh, io.lens, io.y, io.hf, io.hx, io.gates,
+                           io.cs, io.sync, io.status);
+    else if constexpr (kernel_arity(K) == 12)            // lstm_bwd_kernel
+        hipLaunchKernelGGL(K, grid, block, p.lds, st, p.a, p.NC, p.K4p, io.dy, io.gates, io.cs, io.w_hh, io.lens, io.dgx, io.dgf,
+                           io.sync, io.status);
+    else
+        hipLaunchKernelGGL(K, grid, block, p.lds, st, p.a, io.dy, io.gates, io.cs, io.w_hh, io.lens, io.dgx, io.dgf, io.sync, io.status);
+    LAS_LAUNCH_OK();
+    return LAS_OK;
+}
+
+#define ROW(kernel, ...) {launch<kernel<__VA_ARGS__>>, #kernel "<" #__VA_ARGS__ ">", K_##kernel, {__VA_ARGS__}}
+const Row<FwdIo> FWD_ROWS[] = {
+    // <PREC, NB, KS>
+    ROW(lstm_fwd_kernel, LAS_PREC_BF16,1,8), ROW(lstm_fwd_kernel, LAS_PREC_BF16,2,8),
+    ROW(lstm_fwd_kernel, LAS_PREC_BF16,1,10), ROW(lstm_fwd_kernel, LAS_PREC_BF16,2,10),
+    ROW(lstm_fwd_kernel, LAS_PREC_BF16,1,16),
+    ROW(lstm_fwd_kernel, LAS_PREC_BF16,1,32), ROW(lstm_fwd_kernel, LAS_PREC_BF16,2,32),
+    ROW(lstm_fwd_kernel, LAS_PREC_BF16,1,0), ROW(lstm_fwd_kernel, LAS_PREC_BF16,2,0),
+    ROW(lstm_fwd_kernel, LAS_PREC_BF16,4,0), ROW(lstm_fwd_kernel, LAS_PREC_BF16,8,0),
+    ROW(lstm_fwd_kernel, LAS_PREC_F32,1,0), ROW(lstm_fwd_kernel, LAS_PREC_F32,2,0),
+    ROW(lstm_fwd_kernel, LAS_PREC_F32,4,0), ROW(lstm_fwd_kernel, LAS_PREC_F32,8,0),
+    // <NB, KS, SWM, FX>
+    ROW(lstm_fwd_gr_kernel, 1,8,4,false), ROW(lstm_fwd_gr_kernel, 2,8,4,false),
+    ROW(lstm_fwd_gr_kernel, 1,10,4,false), ROW(lstm_fwd_gr_kernel, 2,10,4,false),
+    ROW(lstm_fwd_gr_kernel, 1,16,4,false), ROW(lstm_fwd_gr_kernel, 1,32,8,false),
+    ROW(lstm_fwd_gr_kernel, 1,8,4,true), ROW(lstm_fwd_gr_kernel, 1,10,4,true), ROW(lstm_fwd_gr_kernel, 1,16,4,true),
+    // <KS, FX>
+    ROW(lstm_fwd_x32_kernel, 24,false), ROW(lstm_fwd_x32_kernel, 32,false),
+    ROW(lstm_fwd_x32_kernel, 24,true), ROW(lstm_fwd_x32_kernel, 32,true),
+    // <NB, KS>
+    ROW(lstm_fwd_f32w_kernel, 1,32), ROW(lstm_fwd_f32w_kernel, 1,48), ROW(lstm_fwd_f32w_kernel, 1,64),
+    ROW(lstm_fwd_f32w_kernel, 2,32), ROW(lstm_fwd_f32w_kernel, 2,48), ROW(lstm_fwd_f32w_kernel, 2,64),
+};
+const Row<BwdIo> BWD_ROWS[] = {
+    // <PREC, NB, KS>
+    ROW(lstm_bwd_kernel, LAS_PREC_BF16,1,8), ROW(lstm_bwd_kernel, LAS_PREC_BF16,2,8),
+    ROW(lstm_bwd_kernel, LAS_PREC_BF16,1,10), ROW(lstm_bwd_kernel, LAS_PREC_BF16,2,10),
+    ROW(lstm_bwd_kernel, LAS_PREC_BF16,1,16),
+    ROW(lstm_bwd_kernel, LAS_PREC_BF16,1,0), ROW(lstm_bwd_kernel, LAS_PREC_BF16,2,0),
+    ROW(lstm_bwd_kernel, LAS_PREC_BF16,4,0), ROW(lstm_bwd_kernel, LAS_PREC_BF16,8,0),
+    ROW(lstm_bwd_kernel, LAS_PREC_F32,1,0), ROW(lstm_bwd_kernel, LAS_PREC_F32,2,0),
+    ROW(lstm_bwd_kernel, LAS_PREC_F32,4,0), ROW(lstm_bwd_kernel, LAS_PREC_F32,8,0),
+    // <PREC, NB, MT>
+    ROW(lstm_bwd_ks_kernel, LAS_PREC_BF16,1,5), ROW(lstm_bwd_ks_kernel, LAS_PREC_BF16,1,8), ROW(lstm_bwd_ks_kernel, LAS_PREC_BF16,1,16),
+    ROW(lstm_bwd_ks_kernel, LAS_PREC_BF16,2,5), ROW(lstm_bwd_ks_kernel, LAS_PREC_BF16,2,8), ROW(lstm_bwd_ks_kernel, LAS_PREC_BF16,2,16),
+    ROW(lstm_bwd_ks_kernel, LAS_PREC_F32,1,1), ROW(lstm_bwd_ks_kernel, LAS_PREC_F32,2,1),
+    // <NB, MT, SWM>
+    ROW(lstm_bwd_gr_kernel, 1,5,4), ROW(lstm_bwd_gr_kernel, 1,8,4), ROW(lstm_bwd_gr_kernel, 1,16,12),
+    ROW(lstm_bwd_gr_kernel, 2,5,4), ROW(lstm_bwd_gr_kernel, 2,8,4),
+    // <MT>
+    ROW(lstm_bwd_x32_kernel, 6), ROW(lstm_bwd_x32_kernel, 8),
+    // <NB, MT>
+    ROW(lstm_bwd_f32w_kernel, 1,8), ROW(lstm_bwd_f32w_kernel, 1,12), ROW(lstm_bwd_f32w_kernel, 1,16),
+    ROW(lstm_bwd_f32w_kernel, 2,8), ROW(lstm_bwd_f32w_kernel, 2,12), ROW(lstm_bwd_f32w_kernel, 2,16),
+};
+#undef ROW
+
+template <typename Io, size_t N>
+const Row<Io>* pick(const Row<Io> (&rows)[N], int kernel, int t0, int t1 = 0, int t2 = 0, int t3 = 0) {
+    for (const Row<Io>& r : rows)
+        if (r.kernel == kernel && r.targ[0] == t0 && r.targ[1] == t1 && r.targ[2] == t2 && r.targ[3] == t3) return &r;
+    return nullptr;
+}
+// The plan's last step: the row and what follows from it.  (No such instance: the shape is unsupported.)
+template <typename Io>
+Plan<Io>& select(Plan<Io>& p, const Row<Io>* row, int block, size_t lds, size_t fill, bool twin) {
+    p.rc = row ? LAS_OK : LAS_E_UNSUPPORTED;
+    p.row = row; p.grid = lstm_grid(p.a); p.block = block; p.fill = fill; p.twin = twin;
+    p.lds = lds < MIN_LDS ? MIN_LDS : lds;
+    return p;
+}
+
+// fxI > 0: the layer's input projection fused into the kernel (las_lstm_rec_fwd_fx); only the granule kernel with one batch
+// tile per slice and the 32-unit kernel have such instances, every other choice is LAS_E_UNSUPPORTED then.
+FwdPlan plan_fwd(int prec, int T, int B, int H, int ND, int sr, int concat, int fxI) {
+    FwdPlan p = {};
+    LstmArgs& a = p.a;
+    bool x32;
+    if ((p.rc = plan_args(prec, T, B, H, ND, sr, concat, a, &x32))) return p;
+    p.rc = LAS_E_UNSUPPORTED;                            // until a row is selected
+    const bool fx = fxI > 0, fx_fits = fxI <= 32 * FX_KS && (fxI & 3) == 0 && (long)T * B * fxI * 4 < (1l << 31);
+    if (x32) {
+        p.ws = las_align(fwd_gr_ring_bytes(a));
+        if (fx && !fx_fits) return p;
+        a.fxI = fx ? fxI : 0;
+        return select(p, pick(FWD_ROWS, K_lstm_fwd_x32_kernel, (H + 31) / 32 <= 24 ? 24 : 32, fx), X32_NT, fwd_x32_lds(H),
+                      fwd_gr_ring_bytes(a), true);
+    }
+    // hx holds either ring of the 16-unit geometry: [ND][4][B][Hx] of lstm_fwd_kernel (and the f32w kernels) or the granules
+    // of lstm_fwd_gr_kernel -- the size query answers before the choice between them, and for shapes no kernel takes
+    const size_t esz = prec == LAS_PREC_BF16 ? 2 : 4, vec = prec == LAS_PREC_BF16 ? 8 : 4;
+    const size_t plain = (size_t)ND * HX_SLOTS * B * ((H + vec - 1) / vec * vec) * esz, ring = fwd_gr_ring_bytes(a);
+    p.ws = las_align(plain > ring ? plain : ring);
+    if (ND * ((H + 15) / 16) > las_cu_count()) return p;
+    // more, smaller unit slices when the chip has room (shorter MFMA chains per step): only at H = 512 without XCD grouping
+    // (an XCD-grouped launch beats the finer slicing; beyond 512 two batch slices of 16-unit groups do)
+    int U = 16;
+    if (!a.xl && ND * ((H + 7) / 8) <= las_cu_count() && H == 512) fill_args(a, T, B, H, ND, U = 8, sr, concat);
+    int NB = las_pick_nb(a.Bs);
+    if (NB == 0) return p;
+    // bf16: register-resident weight fragments for the common hidden sizes and small batch slices (VGPR budget:
+    // 4 KS for the weights + the h fragments of a chunk); otherwise the weight slab lives in LDS
+    const int ksteps = (H + 31) / 32;
+    int KS = 0;
+    if (prec == LAS_PREC_BF16 && NB <= 2) {
+        if (!LAS_AB_KNOB("LAS_LSTM_NO_DIRECT")) KS = ksteps <= 8 ? 8 : ksteps <= 10 ? 10 : (ksteps <= 16 && NB == 1) ? 16 : 0;
+        if (KS == 0 && ksteps <= 32 && fwd_lds(prec, H, NB, false) > LDS_CAP) KS = 32;
+    }
+    const size_t lds = fwd_lds(prec, H, NB, KS > 0);
+    if (lds > LDS_CAP) {
+        // fp32 mode: the W_hh slab does not fit LDS -> weight fragments in registers (lstm_f32w.h), 16-unit workgroups
+        if (fx || prec != LAS_PREC_F32) return p;
+        if (U != 16) fill_args(a, T, B, H, ND, 16, sr, concat);
+        NB = las_pick_nb(a.Bs);
+        if (!f32w_ok(prec, H, NB) || fwd_f32w_lds(H, NB) > LDS_CAP) return p;
+        const int ks16 = (H + 15) / 16;
+        return select(p, pick(FWD_ROWS, K_lstm_fwd_f32w_kernel, NB, ks16 <= 32 ? 32 : ks16 <= 48 ? 48 : 64), NT, fwd_f32w_lds(H, NB), 0, false);
+    }
+    // tagged-granule hand-off (lstm_fwd_gr_kernel): no flag, no drain, one barrier per step.  big: KS = 32 (512 < H <= 1024,
+    // one batch tile per slice): the weight fragments take 128 registers per lane, the sweep lists move to LDS and a lane
+    // sweeps up to 8 granules per step
+    const bool big = KS == 32 && NB == 1;
+    const bool gr = prec == LAS_PREC_BF16 && KS > 0 && (KS <= 16 || big) && U == 16 && H % 4 == 0 &&
+                    (long)T * B * ND * 4 * H * 4 < (1l << 31) && (long)H * host_gr_chunks(a.Bs) <= (big ? 2048 : 1024) &&
+                    !las_fallback("LAS_LSTM_NO_GR");
+    if (fx && !(gr && NB == 1 && KS <= 16 && fx_fits)) return p;     // (the caller runs the projection GEMM instead)
+    if (gr) {
+        a.fxI = fx ? fxI : 0;
+        const size_t gr_lds = fwd_gr_lds(H, NB, big ? 8 : 4);
+        select(p, pick(FWD_ROWS, K_lstm_fwd_gr_kernel, NB, KS, big ? 8 : 4, fx), NT + 64, gr_lds, fwd_gr_ring_bytes(a), true);
+        if (big) p.lds = gr_lds;                         // this instance has always taken its request without the MIN_LDS floor
+        return p;
+    }
     // (KS > 16: the weight fragments alone are 128 registers per lane -- one wave per SIMD, no prefetch wave)
-    hipLaunchKernelGGL(k, dim3(lstm_grid(a)), dim3(a.pf && KS <= 16 ? NT + 64 : NT), lds, st, a, xproj, b_ih, b_hh, w_hh, lens, y, hf,
-                       (typename CT<PREC>::T*)hx, gates, cs, sync, status);
-    LAS_LAUNCH_OK();
-    return LAS_OK;
-}
-size_t fwd_gr_lds(int H, int NB, int swm = 4) {
-    const int Kp = (H + 31) / 32 * 32, ld = Kp + 16;
-    return (size_t)2 * NB * 16 * ld * 2 + sizeof(float) * 2 * NB * 16 * (2 * GR_XLD + GR_HLD) + sizeof(int) * (NB * 16 + 4) +
-           (swm > 4 ? sizeof(int) * NT * swm * 2 : 0);
-}
-size_t fwd_gr_ring_bytes(const LstmArgs& a) {
-    return (size_t)16 * a.ND * HX_SLOTS * a.NS * a.H * ((a.Bs >> 4) * 3 + ((a.Bs & 15) + 5) / 6);
-}
-template <int NB, int KS, int SWM = 4, bool FX = false>
-int launch_fwd_gr(const LstmArgs& a, size_t lds, hipStream_t st, const float* xproj, const float* b_ih, const float* b_hh,
-                  const float* w_hh, const int32_t* lens, float* y, float* hf, void* hx, float* gates, float* cs,
-                  SyncWords* sync, int* status) {
-    auto k = lstm_fwd_gr_kernel<NB, KS, SWM, FX>;
-    LAS_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if ((char*)hx != (char*)sync + sizeof(SyncWords))                    // (else: zeroed together with the sync words by the caller below)
-        LAS_HIP(hipMemsetAsync(hx, 0, fwd_gr_ring_bytes(a), st));      // tags of earlier launches must not match
-    hipLaunchKernelGGL(k, dim3(lstm_grid(a)), dim3(NT + 64), lds, st, a, xproj, b_ih, b_hh, w_hh, lens, y, hf,
-                       (u32x4*)hx, gates, cs, sync, status);
-    LAS_LAUNCH_OK();
-    return LAS_OK;
-}
-template <int PREC, int NB, int KS>
-int launch_bwd(const LstmArgs& a, int NC, int K4p, size_t lds, hipStream_t st, const float* dy, const float* gates,
-               const float* cs, const float* w_hh, const int32_t* lens, void* dgx, float* dgf, SyncWords* sync,
-               int* status) {
-    auto k = lstm_bwd_kernel<PREC, NB, KS>;
-    LAS_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k, dim3(lstm_grid(a)), dim3(NT), lds, st, a, NC, K4p, dy, gates, cs, w_hh, lens,
-                       (typename CT<PREC>::T*)dgx, dgf, sync, status);
-    LAS_LAUNCH_OK();
-    return LAS_OK;
+    return select(p, pick(FWD_ROWS, K_lstm_fwd_kernel, prec, NB, KS), a.pf && KS <= 16 ? NT + 64 : NT, lds, 0, false);
 }
 
-
-// Which backward kernel a shape gets, its LDS request and the size of its exchange workspace (`dgx`).
-struct BwdPlan { bool ks, wdirect, gr, f32w; int NB, NC, K4p; size_t lds, ws; };
-int bwd_plan_lds(int prec, int T, int B, int H, int ND, const LstmArgs& a, BwdPlan& p);
-int bwd_plan(int prec, int T, int B, int H, int ND, const LstmArgs& a, BwdPlan& p) {
-    p.f32w = false;
-    const int rc = bwd_plan_lds(prec, T, B, H, ND, a, p);
-    // fp32 mode, no LDS placement of W_hh fits: the K-split kernel with its weight fragments in registers (lstm_f32w.h)
-    if (rc != LAS_E_UNSUPPORTED || !f32w_ok(prec, H, p.NB) || ND * ((H + 15) / 16) > las_cu_count() ||
-        bwd_f32w_lds(H, p.NB) > LDS_CAP) return rc;
-    p.ks = p.f32w = true; p.wdirect = p.gr = false;
+BwdPlan plan_bwd(int prec, int T, int B, int H, int ND, int sr, int concat) {
+    BwdPlan p = {};
+    LstmArgs& a = p.a;
+    bool x32;
+    if ((p.rc = plan_args(prec, T, B, H, ND, sr, concat, a, &x32))) return p;
+    p.rc = LAS_E_UNSUPPORTED;                            // until a row is selected
     p.NC = 1; p.K4p = 4 * H;
-    p.lds = bwd_f32w_lds(H, p.NB);
-    p.ws = bwd_ks_ring_bytes(prec, H, ND, a.NS, p.NB);
-    if (p.lds < MIN_LDS) p.lds = MIN_LDS;
-    return LAS_OK;
-}
-int bwd_plan_lds(int prec, int T, int B, int H, int ND, const LstmArgs& a, BwdPlan& p) {
-    p.NB = las_pick_nb(a.Bs);
-    if (p.NB == 0 || ND * ((H + 15) / 16) > las_cu_count()) return LAS_E_UNSUPPORTED;
+    if (x32) {
+        p.ws = bwd_x32_ring_bytes(a);
+        return select(p, pick(BWD_ROWS, K_lstm_bwd_x32_kernel, ((H + 15) / 16 + 7) / 8 <= 6 ? 6 : 8), X32_NT, bwd_x32_lds(), p.ws, true);
+    }
+    const bool bf16 = prec == LAS_PREC_BF16;
+    const int NB = las_pick_nb(a.Bs), mt = (a.G + 3) / 4;         // mt: 16-column tiles (consumers) per wave
+    if (NB == 0 || ND * a.G > las_cu_count()) return p;
     // K-split exchange (reduce-scatter of partial dh) whenever it fits: the [H][64] weight slab in LDS, or (bf16) the
     // weight fragments fetched from global memory into registers (ceil(G / 4) <= 16 tiles per wave: H <= 1024)
-    p.ks = false; p.wdirect = false;
-    if (p.NB <= 2 && !LAS_AB_KNOB("LAS_LSTM_BWD_GATHER")) {
-        const int mt = (a.G + 3) / 4;
-        if (bwd_ks_lds(prec, H, p.NB, false) <= LDS_CAP && (prec != LAS_PREC_BF16 || mt <= 16)) p.ks = true;
-        else if (prec == LAS_PREC_BF16 && mt <= 16 && bwd_ks_lds(prec, H, p.NB, true) <= LDS_CAP) p.ks = p.wdirect = true;
+    bool ks = false, wdirect = false;
+    if (NB <= 2 && !LAS_AB_KNOB("LAS_LSTM_BWD_GATHER")) {
+        if (bwd_ks_lds(prec, H, NB, false) <= LDS_CAP && (!bf16 || mt <= 16)) ks = true;
+        else if (bf16 && mt <= 16 && bwd_ks_lds(prec, H, NB, true) <= LDS_CAP) ks = wdirect = true;
     }
     // tagged-granule hand-off (lstm_bwd_gr_kernel): bf16, <= 8 consumers per wave, <= 1 024 granules per inbox and step
     // (more than 32 producers -- 512 < H <= 1024 --: one batch tile per slice, up to 12 granules per lane and step, lists in LDS)
-    const int mt_ = (a.G + 3) / 4;
-    p.gr = p.ks && prec == LAS_PREC_BF16 && (mt_ <= 8 || (mt_ <= 16 && p.NB == 1)) && H % 4 == 0 &&
-           (long)a.G * a.Bs * 4 <= (mt_ > 8 ? 3072 : 1024) &&
-           (long)T * B * ND * 4 * H * 4 < (1l << 31) && bwd_gr_lds(H, p.NB) <= LDS_CAP && !las_fallback("LAS_LSTM_NO_GR");
-    if (p.gr) {
-        p.wdirect = false;
-        p.lds = bwd_gr_lds(H, p.NB);
+    const bool gr = ks && bf16 && (mt <= 8 || (mt <= 16 && NB == 1)) && H % 4 == 0 && (long)a.G * a.Bs * 4 <= (mt > 8 ? 3072 : 1024) &&
+                    (long)T * B * ND * 4 * H * 4 < (1l << 31) && bwd_gr_lds(H, NB) <= LDS_CAP && !las_fallback("LAS_LSTM_NO_GR");
+    const int mt3 = mt <= 5 ? 5 : mt <= 8 ? 8 : 16;
+    if (gr) {
         p.ws = bwd_gr_ring_bytes(a);
-        p.NC = 1; p.K4p = 4 * H;
-    } else if (p.ks) {
-        p.lds = bwd_ks_lds(prec, H, p.NB, p.wdirect);
-        p.ws = bwd_ks_ring_bytes(prec, H, ND, a.NS, p.NB);
-        p.NC = 1; p.K4p = 4 * H;
-    } else {
-        const int ks = prec == LAS_PREC_BF16 ? 32 : 16;
-        p.K4p = bwd_k4p(prec, H);
-        p.NC = 1;                                              // chunks must keep whole k-steps per wave and be unpadded if >1
-        while (p.NC <= 8 && (bwd_lds(prec, H, p.NB, p.NC) > LDS_CAP || (p.K4p / p.NC) % (4 * ks) != 0 || (p.NC > 1 && p.K4p != 4 * H))) p.NC *= 2;
-        if (p.NC > 8) return LAS_E_UNSUPPORTED;
-        p.lds = bwd_lds(prec, H, p.NB, p.NC);
-        p.ws = (size_t)ND * T * B * 4 * H * (prec == LAS_PREC_BF16 ? 2 : 4);    // all-gather variant: dgates copy
+        return select(p, pick(BWD_ROWS, K_lstm_bwd_gr_kernel, NB, mt3, mt > 8 ? 12 : 4), NT + 64, bwd_gr_lds(H, NB), p.ws, true);
     }
-    if (p.lds < MIN_LDS) p.lds = MIN_LDS;
+    if (ks) {
+        a.wdirect = wdirect ? 1 : 0;
+        p.ws = bwd_ks_ring_bytes(prec, H, ND, a.NS, NB);
+        return select(p, pick(BWD_ROWS, K_lstm_bwd_ks_kernel, prec, NB, bf16 ? mt3 : 1), NT, bwd_ks_lds(prec, H, NB, wdirect), 0, false);
+    }
+    // all-gather of the d gates (lstm_bwd_kernel); chunks must keep whole k-steps per wave and be unpadded if > 1
+    const int kstep = bf16 ? 32 : 16;
+    p.K4p = bwd_k4p(prec, H);
+    while (p.NC <= 8 && (bwd_lds(prec, H, NB, p.NC) > LDS_CAP || (p.K4p / p.NC) % (4 * kstep) != 0 || (p.NC > 1 && p.K4p != 4 * H))) p.NC *= 2;
+    if (p.NC <= 8) {
+        p.ws = (size_t)ND * T * B * 4 * H * (bf16 ? 2 : 4);       // the d gates copy
+        const int kq = p.K4p / 32 / 4;                            // k-steps per wave
+        const bool direct = bf16 && NB <= 2 && p.NC == 1 && !LAS_AB_KNOB("LAS_LSTM_NO_DIRECT");
+        const int KS = direct && (kq == 8 || kq == 10 || (kq == 16 && NB == 1)) ? kq : 0;
+        return select(p, pick(BWD_ROWS, K_lstm_bwd_kernel, prec, NB, KS), NT, bwd_lds(prec, H, NB, p.NC), 0, false);
+    }
+    // fp32 mode, no LDS placement of W_hh fits: the K-split kernel with its weight fragments in registers (lstm_f32w.h)
+    if (!f32w_ok(prec, H, NB) || bwd_f32w_lds(H, NB) > LDS_CAP) return p;
+    p.NC = 1; p.K4p = 4 * H;
+    p.ws = bwd_ks_ring_bytes(prec, H, ND, a.NS, NB);
+    return select(p, pick(BWD_ROWS, K_lstm_bwd_f32w_kernel, NB, mt <= 8 ? 8 : mt <= 12 ? 12 : 16), NT, bwd_f32w_lds(H, NB), 0, false);
+}
+
+// Zero the sync words and, for the kernels that have one, the exchange ring: one fill when the caller placed the ring right
+// behind the sync words, two otherwise.
+int zero_sync_and_ring(void* sync, void* ring, size_t ring_bytes, hipStream_t st) {
+    const bool behind = ring_bytes && (char*)ring == (char*)sync + sizeof(SyncWords);
+    LAS_HIP(hipMemsetAsync(sync, 0, sizeof(SyncWords) + (behind ? ring_bytes : 0), st));
+    if (ring_bytes && !behind) LAS_HIP(hipMemsetAsync(ring, 0, ring_bytes, st));
     return LAS_OK;
+}
+
+template <typename Io>
+int describe(const Plan<Io>& p, char* buf, size_t cap) {
+    snprintf(buf, cap, "%s grid=%d block=%d lds=%zu fill=%zu ws=%zu twin=%d", p.rc == LAS_OK ? p.row->name : "-", p.grid, p.block,
+             p.lds, p.fill, p.ws, p.twin ? 1 : 0);
+    return p.rc;
+}
+
+// y_bf16 (may be null): the bf16 twin of y, [T_out][B][F_out] -- the operand of the projection GEMM behind the layer.  The granule
+// and 32-unit kernels write it next to the fp32 stores (no second pass over y); behind the other kernels it is one cast pass.
+// fxI > 0: `xproj` is the layer input x [T][B][fxI] and w_ih its projection weights (las_lstm_rec_fwd_fx).
+int rec_fwd(int prec, const float* xproj, int fxI, const float* w_ih, const float* b_ih, const float* b_hh, const float* w_hh,
+            const int32_t* lens, int T, int B, int H, int ND, int sr, int concat, float* y, float* hf, void* y_bf16, void* hx,
+            float* gates, float* cs, void* sync, int* status, void* stream) {
+    LAS_CHECK_ARG(xproj && b_ih && b_hh && w_hh && lens && y && hf && hx && gates && cs && sync && status);
+    LAS_CHECK_ARG(prec == LAS_PREC_BF16 || prec == LAS_PREC_F32);
+    FwdPlan p = plan_fwd(prec, T, B, H, ND, sr, concat, fxI);
+    if (p.rc) return p.rc;
+    p.a.w_ih = w_ih; p.a.tw = y_bf16; p.a.y_is_hf = (y == hf);
+    if (p.a.y_is_hf && sr != 1) return LAS_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = zero_sync_and_ring(sync, hx, p.fill, st);
+    if (rc == LAS_OK) rc = p.row->launch(p, FwdIo{xproj, b_ih, b_hh, w_hh, lens, y, hf, {hx}, gates, cs, (SyncWords*)sync, status}, st);
+    if (rc == LAS_OK && y_bf16 && !p.twin) rc = las_cast_bf16(y, y_bf16, (int64_t)p.a.T_out * B * p.a.F_out, stream);
+    return rc;
 }
 
 }  // namespace
@@ -1899,353 +2097,69 @@ extern "C" void las_lstm_out_shape(int T, int H, int ND, int sr, int concat, int
 
 extern "C" size_t las_lstm_sync_bytes(void) { return sizeof(SyncWords); }
 
-extern "C" size_t las_lstm_hx_bytes(int prec, int T, int B, int H, int ND) {
-    LstmArgs a;
-    if (check_common(T, B, H, ND, 1)) return 0;
-    if (use_x32(prec, T, B, H, ND, 1, 0, a)) return las_align(fwd_gr_ring_bytes(a));
-    fill_args(a, T, B, H, ND, 16, 1, 0);
-    const size_t esz = prec == LAS_PREC_BF16 ? 2 : 4, vec = prec == LAS_PREC_BF16 ? 8 : 4;
-    const size_t plain = (size_t)ND * HX_SLOTS * B * ((H + vec - 1) / vec * vec) * esz;     // [ND][4][B][Hx] ring of lstm_fwd_kernel
-    const size_t gr = fwd_gr_ring_bytes(a);                                                 // granule ring of lstm_fwd_gr_kernel
-    return las_align(plain > gr ? plain : gr);
-}
+extern "C" size_t las_lstm_hx_bytes(int prec, int T, int B, int H, int ND) { return plan_fwd(prec, T, B, H, ND, 1, 0, 0).ws; }
 
 extern "C" size_t las_lstm_bwd_ws_bytes(int prec, int T, int B, int H, int ND) {
-    LstmArgs a;
-    BwdPlan p;
-    if (check_common(T, B, H, ND, 1)) return 0;
-    if (use_x32(prec, T, B, H, ND, 1, 0, a)) return bwd_x32_ring_bytes(a);
-    fill_args(a, T, B, H, ND, 16, 1, 0);
-    return bwd_plan(prec, T, B, H, ND, a, p) == LAS_OK ? p.ws : 0;
+    const BwdPlan p = plan_bwd(prec, T, B, H, ND, 1, 0);
+    return p.rc == LAS_OK ? p.ws : 0;
 }
 
 extern "C" int las_lstm_bwd_is_ksplit(int prec, int T, int B, int H, int ND) {
-    LstmArgs a;
-    BwdPlan p;
-    if (check_common(T, B, H, ND, 1)) return 0;
-    if (use_x32(prec, T, B, H, ND, 1, 0, a)) return 3;
-    fill_args(a, T, B, H, ND, 16, 1, 0);
-    if (bwd_plan(prec, T, B, H, ND, a, p) != LAS_OK) return 0;
-    return p.gr ? 2 : p.ks ? 1 : 0;
+    const BwdPlan p = plan_bwd(prec, T, B, H, ND, 1, 0);
+    return p.rc == LAS_OK ? variant_code(p.row->kernel) : 0;
+}
+
+extern "C" int las_lstm_fwd_variant(int prec, int T, int B, int H, int ND) {
+    const FwdPlan p = plan_fwd(prec, T, B, H, ND, 1, 0, 0);
+    return p.rc == LAS_OK ? variant_code(p.row->kernel) : 0;
 }
 
 extern "C" int las_lstm_resident_wgs(int prec, int T, int B, int H, int ND) {
-    LstmArgs a;
-    (void)prec;
-    if (check_common(T, B, H, ND, 1)) return 0;
-    if (use_x32(prec, T, B, H, ND, 1, 0, a)) return a.ND * a.G * a.NS;
-    fill_args(a, T, B, H, ND, 16, 1, 0);
+    const LstmArgs a = plan_bwd(prec, T, B, H, ND, 1, 0).a;           // (all zero when the arguments are rejected)
     return a.ND * a.G * a.NS;            // (an XCD-grouped launch starts more, the ones without a group exit at once)
 }
 
-// 1: lstm_fwd_gr_kernel (tagged-granule hand-off), 0: lstm_fwd_kernel.  Same rule as in las_lstm_rec_fwd below.
-static bool fwd_uses_gr(int prec, int T, int B, int H, int ND, const LstmArgs& a, int U, int NB, int KS) {
-    // KS = 32 (512 < H <= 1024, one batch tile per slice): the weight fragments take 128 registers per lane, the sweep lists
-    // move to LDS and a lane sweeps up to 8 granules per step
-    const bool big = KS == 32 && NB == 1;
-    return prec == LAS_PREC_BF16 && KS > 0 && (KS <= 16 || big) && U == 16 && H % 4 == 0 && (long)T * B * ND * 4 * H * 4 < (1l << 31) &&
-           (long)H * ((a.Bs >> 4) * 3 + ((a.Bs & 15) + 5) / 6) <= (big ? 2048 : 1024) && !las_fallback("LAS_LSTM_NO_GR");
-}
-extern "C" int las_lstm_fwd_variant(int prec, int T, int B, int H, int ND) {
-    LstmArgs a;
-    if (check_common(T, B, H, ND, 1)) return 0;
-    if (use_x32(prec, T, B, H, ND, 1, 0, a)) return 2;
-    if (ND * ((H + 15) / 16) > las_cu_count()) return 0;
-    fill_args(a, T, B, H, ND, 16, 1, 0);
-    const int NB = las_pick_nb(a.Bs), ksteps = (H + 31) / 32;
-    int KS = 0;
-    if (prec == LAS_PREC_BF16 && NB >= 1 && NB <= 2 && !LAS_AB_KNOB("LAS_LSTM_NO_DIRECT"))
-        KS = ksteps <= 8 ? 8 : ksteps <= 10 ? 10 : (ksteps <= 16 && NB == 1) ? 16 : 0;
-    if (prec == LAS_PREC_BF16 && NB >= 1 && NB <= 2 && KS == 0 && ksteps <= 32 && fwd_lds(prec, H, NB, false) > LDS_CAP) KS = 32;     // (as las_lstm_rec_fwd)
-    const bool u8 = !a.xl && ND * ((H + 7) / 8) <= las_cu_count() && H == 512;
-    return fwd_uses_gr(prec, T, B, H, ND, a, u8 ? 8 : 16, NB, KS) ? 1 : 0;
+extern "C" int las_lstm_fwd_fx_ok(int prec, int T, int B, int H, int ND, int I) {
+    return I > 0 && plan_fwd(prec, T, B, H, ND, 1, 0, I).rc == LAS_OK;
 }
 
-static int rec_fwd_impl(int prec, const float* xproj, const float* b_ih, const float* b_hh, const float* w_hh,
-                        const int32_t* lens, int T, int B, int H, int ND, int sr, int concat, float* y,
-                        float* hf, void* tw, bool* tw_done, void* hx, float* gates, float* cs, void* sync, int* status, void* stream,
-                        int fxI = 0, const float* w_ih = nullptr);
+extern "C" int las_lstm_plan_describe(int prec, int T, int B, int H, int ND, int sr, int concat, int I, int backward, char* buf,
+                                      size_t cap) {
+    LAS_CHECK_ARG(buf && cap > 0 && (prec == LAS_PREC_BF16 || prec == LAS_PREC_F32));
+    return backward ? describe(plan_bwd(prec, T, B, H, ND, sr, concat), buf, cap)
+                    : describe(plan_fwd(prec, T, B, H, ND, sr, concat, I), buf, cap);
+}
 
-// y_bf16 (may be null): the bf16 twin of y, [T_out][B][F_out] -- the operand of the projection GEMM behind the layer.  The granule
-// and 32-unit kernels write it next to the fp32 stores (no second pass over y); behind the other kernels it is one cast pass.
 extern "C" int las_lstm_rec_fwd(int prec, const float* xproj, const float* b_ih, const float* b_hh, const float* w_hh,
                                 const int32_t* lens, int T, int B, int H, int ND, int sr, int concat, float* y,
                                 float* hf, void* y_bf16, void* hx, float* gates, float* cs, void* sync, int* status, void* stream) {
-    bool in_kernel = false;
-    int rc = rec_fwd_impl(prec, xproj, b_ih, b_hh, w_hh, lens, T, B, H, ND, sr, concat, y, hf, y_bf16, &in_kernel, hx, gates,
-                          cs, sync, status, stream);
-    if (rc == LAS_OK && y_bf16 && !in_kernel) {
-        int T_out, F_out;
-        las_lstm_out_shape(T, H, ND, sr, concat, &T_out, &F_out);
-        rc = las_cast_bf16(y, y_bf16, (int64_t)T_out * B * F_out, stream);
-    }
-    return rc;
-}
-
-static int rec_fwd_impl(int prec, const float* xproj, const float* b_ih, const float* b_hh, const float* w_hh,
-                        const int32_t* lens, int T, int B, int H, int ND, int sr, int concat, float* y,
-                        float* hf, void* tw, bool* tw_done, void* hx, float* gates, float* cs, void* sync, int* status, void* stream,
-                        int fxI, const float* w_ih) {
-    LAS_CHECK_ARG(xproj && b_ih && b_hh && w_hh && lens && y && hf && hx && gates && cs && sync && status);
-    int rc = check_common(T, B, H, ND, sr);
-    if (rc) return rc;
-    if (prec != LAS_PREC_BF16 && prec != LAS_PREC_F32) return LAS_E_BADARG;
-    int U = 16;
-    LstmArgs a;
-    if (use_x32(prec, T, B, H, ND, sr, concat, a)) {
-        if (fxI > 0 && (fxI > 32 * FX_KS || (fxI & 3) || (long)T * B * fxI * 4 >= (1l << 31))) return LAS_E_UNSUPPORTED;
-        a.fxI = fxI; a.w_ih = w_ih;
-        a.y_is_hf = (y == hf);
-        a.tw = tw; *tw_done = true;
-        if (a.y_is_hf && sr != 1) return LAS_E_BADARG;
-        hipStream_t st = (hipStream_t)stream;
-        const size_t ringb = fwd_gr_ring_bytes(a);
-        const bool behind = (char*)hx == (char*)sync + sizeof(SyncWords);
-        LAS_HIP(hipMemsetAsync(sync, 0, sizeof(SyncWords) + (behind ? ringb : 0), st));
-        if (!behind) LAS_HIP(hipMemsetAsync(hx, 0, ringb, st));
-        size_t lds = fwd_x32_lds(H);
-        if (lds < MIN_LDS) lds = MIN_LDS;
-#define LAS_X32_FWD(KS_)                                                                                                   \
-    {                                                                                                                     \
-        auto k = fxI > 0 ? lstm_fwd_x32_kernel<KS_, true> : lstm_fwd_x32_kernel<KS_, false>;                              \
-        LAS_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));               \
-        hipLaunchKernelGGL(k, dim3(lstm_grid(a)), dim3(X32_NT), lds, st, a, xproj, b_ih, b_hh, w_hh, lens, y, hf, (u32x4*)hx, \
-                           gates, cs, (SyncWords*)sync, status);                                                          \
-        LAS_LAUNCH_OK();                                                                                                  \
-        return LAS_OK;                                                                                                    \
-    }
-        if ((H + 31) / 32 <= 24) LAS_X32_FWD(24) else LAS_X32_FWD(32)
-#undef LAS_X32_FWD
-    }
-    if (ND * ((H + 15) / 16) > las_cu_count()) return LAS_E_UNSUPPORTED;
-    // use more, smaller unit slices when the chip has room (shorter MFMA chains per step)
-    fill_args(a, T, B, H, ND, U, sr, concat);
-    if (!a.xl && ND * ((H + 7) / 8) <= las_cu_count() && H >= 512 && H <= 512) {      // (an XCD-grouped launch beats the finer slicing;
-        U = 8;                                                            // beyond 512 two batch slices of 16-unit groups do)
-        fill_args(a, T, B, H, ND, U, sr, concat);
-    }
-    const int NB = las_pick_nb(a.Bs);
-    if (NB == 0) return LAS_E_UNSUPPORTED;
-    // bf16: register-resident weight fragments for the common hidden sizes and small batch slices (VGPR budget:
-    // 4 KS for the weights + the h fragments of a chunk); otherwise the weight slab lives in LDS
-    const int ksteps = (H + 31) / 32;
-    int KS = 0;
-    if (prec == LAS_PREC_BF16 && NB <= 2 && !LAS_AB_KNOB("LAS_LSTM_NO_DIRECT")) {
-        if (ksteps <= 8) KS = 8;
-        else if (ksteps <= 10) KS = 10;
-        else if (ksteps <= 16 && NB == 1) KS = 16;
-    }
-    if (prec == LAS_PREC_BF16 && NB <= 2 && KS == 0 && ksteps <= 32 && fwd_lds(prec, H, NB, false) > LDS_CAP) KS = 32;
-    size_t lds = fwd_lds(prec, H, NB, KS > 0);
-    if (lds > LDS_CAP) {
-        // fp32 mode: the W_hh slab does not fit LDS -> weight fragments in registers (lstm_f32w.h), 16-unit workgroups
-        if (fxI > 0 || prec != LAS_PREC_F32) return LAS_E_UNSUPPORTED;
-        if (U != 16) fill_args(a, T, B, H, ND, 16, sr, concat);
-        if (!f32w_ok(prec, H, las_pick_nb(a.Bs)) || fwd_f32w_lds(H, las_pick_nb(a.Bs)) > LDS_CAP) return LAS_E_UNSUPPORTED;
-        a.y_is_hf = (y == hf);
-        a.tw = tw;
-        if (a.y_is_hf && sr != 1) return LAS_E_BADARG;
-        lds = fwd_f32w_lds(H, las_pick_nb(a.Bs));
-        if (lds < MIN_LDS) lds = MIN_LDS;
-        hipStream_t st = (hipStream_t)stream;
-        LAS_HIP(hipMemsetAsync(sync, 0, sizeof(SyncWords), st));
-#define LAS_F32W_FWD(N_, K_)                                                                                            \
-    {                                                                                                                 \
-        auto k = lstm_fwd_f32w_kernel<N_, K_>;                                                                        \
-        LAS_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));           \
-        hipLaunchKernelGGL(k, dim3(lstm_grid(a)), dim3(NT), lds, st, a, xproj, b_ih, b_hh, w_hh, lens, y, hf, (float*)hx, \
-                           gates, cs, (SyncWords*)sync, status);                                                      \
-        LAS_LAUNCH_OK();                                                                                              \
-        return LAS_OK;                                                                                                \
-    }
-        const int ks16 = (H + 15) / 16;
-        if (las_pick_nb(a.Bs) == 1) { if (ks16 <= 32) LAS_F32W_FWD(1, 32) else if (ks16 <= 48) LAS_F32W_FWD(1, 48) else LAS_F32W_FWD(1, 64) }
-        else { if (ks16 <= 32) LAS_F32W_FWD(2, 32) else if (ks16 <= 48) LAS_F32W_FWD(2, 48) else LAS_F32W_FWD(2, 64) }
-#undef LAS_F32W_FWD
-    }
-    a.y_is_hf = (y == hf);
-    a.tw = tw;
-    if (a.y_is_hf && sr != 1) return LAS_E_BADARG;
-    if (lds < MIN_LDS) lds = MIN_LDS;
-    hipStream_t st = (hipStream_t)stream;
-    // one fill for the sync words and, when the caller placed it right behind them, the granule ring
-    const bool gr_fwd = fwd_uses_gr(prec, T, B, H, ND, a, U, NB, KS);
-    LAS_HIP(hipMemsetAsync(sync, 0, sizeof(SyncWords) + ((gr_fwd && (char*)hx == (char*)sync + sizeof(SyncWords)) ? fwd_gr_ring_bytes(a) : 0), st));
-#define LAS_FWD_ARGS a, lds, st, xproj, b_ih, b_hh, w_hh, lens, y, hf, hx, gates, cs, (SyncWords*)sync, status
-    if (fxI > 0 && !(gr_fwd && NB == 1 && KS >= 8 && KS <= 16 && fxI <= 32 * FX_KS && (fxI & 3) == 0 && (long)T * B * fxI * 4 < (1l << 31)))
-        return LAS_E_UNSUPPORTED;                        // (las_lstm_fwd_fx_ok: the caller runs the projection GEMM instead)
-    if (gr_fwd) {
-        *tw_done = true;
-        // tagged-granule hand-off (lstm_fwd_gr_kernel): no flag, no drain, one barrier per step
-        lds = fwd_gr_lds(H, NB);
-        if (lds < MIN_LDS) lds = MIN_LDS;
-        if (fxI > 0) {                                   // fused input projection: `xproj` is the layer input
-            a.fxI = fxI; a.w_ih = w_ih;
-            if (KS == 8) return launch_fwd_gr<1, 8, 4, true>(LAS_FWD_ARGS);
-            if (KS == 10) return launch_fwd_gr<1, 10, 4, true>(LAS_FWD_ARGS);
-            return launch_fwd_gr<1, 16, 4, true>(LAS_FWD_ARGS);
-        }
-        if (KS == 8)  { LAS_NB_SWITCH(NB, return (launch_fwd_gr<NB_ <= 2 ? NB_ : 1, 8>(LAS_FWD_ARGS))); }
-        if (KS == 10) { LAS_NB_SWITCH(NB, return (launch_fwd_gr<NB_ <= 2 ? NB_ : 1, 10>(LAS_FWD_ARGS))); }
-        if (KS == 16) { return launch_fwd_gr<1, 16>(LAS_FWD_ARGS); }
-        if (KS == 32) { lds = fwd_gr_lds(H, 1, 8); return launch_fwd_gr<1, 32, 8>(LAS_FWD_ARGS); }
-    }
-    if (prec == LAS_PREC_BF16) {
-        if (KS == 8)  { LAS_NB_SWITCH(NB, return (launch_fwd<LAS_PREC_BF16, NB_ <= 2 ? NB_ : 1, 8>(LAS_FWD_ARGS))); }
-        if (KS == 10) { LAS_NB_SWITCH(NB, return (launch_fwd<LAS_PREC_BF16, NB_ <= 2 ? NB_ : 1, 10>(LAS_FWD_ARGS))); }
-        if (KS == 16) { return launch_fwd<LAS_PREC_BF16, 1, 16>(LAS_FWD_ARGS); }
-        if (KS == 32) { LAS_NB_SWITCH(NB, return (launch_fwd<LAS_PREC_BF16, NB_ <= 2 ? NB_ : 1, 32>(LAS_FWD_ARGS))); }
-        LAS_NB_SWITCH(NB, return (launch_fwd<LAS_PREC_BF16, NB_, 0>(LAS_FWD_ARGS)));
-    } else {
-        LAS_NB_SWITCH(NB, return (launch_fwd<LAS_PREC_F32, NB_, 0>(LAS_FWD_ARGS)));
-    }
-#undef LAS_FWD_ARGS
-    return LAS_E_BADARG;
+    return rec_fwd(prec, xproj, 0, nullptr, b_ih, b_hh, w_hh, lens, T, B, H, ND, sr, concat, y, hf, y_bf16, hx, gates, cs, sync,
+                   status, stream);
 }
 
 // The same with the layer's input projection FUSED (bf16 mode, granule kernel with one batch tile per slice, input width I <= 96
 // and a multiple of 4: las_lstm_fwd_fx_ok): x [T][B][I] and w_ih [ND*4H][I] instead of xproj = x W_ih^T -- the bottom layer's
 // projection GEMM (K = 80: pure output traffic) and the kernel's read-back of its 4H-wide rows disappear.
-extern "C" int las_lstm_fwd_fx_ok(int prec, int T, int B, int H, int ND, int I) {
-    if (prec != LAS_PREC_BF16 || I < 4 || I > 32 * FX_KS || (I & 3) || (long)T * B * I * 4 >= (1l << 31)) return 0;
-    const int var = las_lstm_fwd_variant(prec, T, B, H, ND);
-    if (var == 2) return 1;                              // the 32-unit kernel: one batch tile by construction
-    if (var != 1) return 0;
-    LstmArgs a;
-    fill_args(a, T, B, H, ND, 16, 1, 0);
-    const int ksteps = (H + 31) / 32;
-    return las_pick_nb(a.Bs) == 1 && ksteps <= 16 && !(ND * ((H + 7) / 8) <= las_cu_count() && !a.xl && H == 512);
-}
 extern "C" int las_lstm_rec_fwd_fx(int prec, const float* x, int I, const float* w_ih, const float* b_ih, const float* b_hh,
                                    const float* w_hh, const int32_t* lens, int T, int B, int H, int ND, int sr, int concat, float* y,
                                    float* hf, void* y_bf16, void* hx, float* gates, float* cs, void* sync, int* status, void* stream) {
     LAS_CHECK_ARG(x && w_ih && I > 0);
-    bool in_kernel = false;
-    int rc = rec_fwd_impl(prec, x, b_ih, b_hh, w_hh, lens, T, B, H, ND, sr, concat, y, hf, y_bf16, &in_kernel, hx, gates, cs, sync,
-                          status, stream, I, w_ih);
-    if (rc == LAS_OK && y_bf16 && !in_kernel) {
-        int T_out, F_out;
-        las_lstm_out_shape(T, H, ND, sr, concat, &T_out, &F_out);
-        rc = las_cast_bf16(y, y_bf16, (int64_t)T_out * B * F_out, stream);
-    }
-    return rc;
+    return rec_fwd(prec, x, I, w_ih, b_ih, b_hh, w_hh, lens, T, B, H, ND, sr, concat, y, hf, y_bf16, hx, gates, cs, sync, status, stream);
 }
-
-static int rec_bwd_impl(int prec, const float* dy, const float* gates, const float* cs, const float* w_hh,
-                        const int32_t* lens, int T, int B, int H, int ND, int sr, int concat, void* dgx,
-                        float* dgf, void* tw, bool* tw_done, void* sync, int* status, void* stream);
 
 // dgf_bf16 (may be null): the bf16 twin of dgf, [T][B][ND*4H] -- the operand of the d x / d W_ih / d W_hh GEMMs behind the launch;
 // written by the granule and 32-unit kernels themselves, one cast pass behind the others.
 extern "C" int las_lstm_rec_bwd(int prec, const float* dy, const float* gates, const float* cs, const float* w_hh,
                                 const int32_t* lens, int T, int B, int H, int ND, int sr, int concat, void* dgx,
                                 float* dgf, void* dgf_bf16, void* sync, int* status, void* stream) {
-    bool in_kernel = false;
-    int rc = rec_bwd_impl(prec, dy, gates, cs, w_hh, lens, T, B, H, ND, sr, concat, dgx, dgf, dgf_bf16, &in_kernel, sync, status, stream);
-    if (rc == LAS_OK && dgf_bf16 && !in_kernel) rc = las_cast_bf16(dgf, dgf_bf16, (int64_t)T * B * ND * 4 * H, stream);
-    return rc;
-}
-
-static int rec_bwd_impl(int prec, const float* dy, const float* gates, const float* cs, const float* w_hh,
-                        const int32_t* lens, int T, int B, int H, int ND, int sr, int concat, void* dgx,
-                        float* dgf, void* tw, bool* tw_done, void* sync, int* status, void* stream) {
     LAS_CHECK_ARG(dy && gates && cs && w_hh && lens && dgx && dgf && sync && status);
-    int rc = check_common(T, B, H, ND, sr);
-    if (rc) return rc;
-    if (prec != LAS_PREC_BF16 && prec != LAS_PREC_F32) return LAS_E_BADARG;
-    LstmArgs a;
-    if (use_x32(prec, T, B, H, ND, sr, concat, a)) {
-        a.tw = tw; *tw_done = true;
-        hipStream_t st = (hipStream_t)stream;
-        const size_t ringb = bwd_x32_ring_bytes(a);
-        const bool behind = (char*)dgx == (char*)sync + sizeof(SyncWords);
-        LAS_HIP(hipMemsetAsync(sync, 0, sizeof(SyncWords) + (behind ? ringb : 0), st));
-        if (!behind) LAS_HIP(hipMemsetAsync(dgx, 0, ringb, st));
-        size_t lds = bwd_x32_lds();
-        if (lds < MIN_LDS) lds = MIN_LDS;
-#define LAS_X32_BWD(MT_)                                                                                                   \
-    {                                                                                                                     \
-        auto k = lstm_bwd_x32_kernel<MT_>;                                                                                \
-        LAS_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));               \
-        hipLaunchKernelGGL(k, dim3(lstm_grid(a)), dim3(X32_NT), lds, st, a, dy, gates, cs, w_hh, lens, (u32x4*)dgx, dgf,   \
-                           (SyncWords*)sync, status);                                                                     \
-        LAS_LAUNCH_OK();                                                                                                  \
-        return LAS_OK;                                                                                                    \
-    }
-        if (((H + 15) / 16 + 7) / 8 <= 6) LAS_X32_BWD(6) else LAS_X32_BWD(8)
-#undef LAS_X32_BWD
-    }
-    fill_args(a, T, B, H, ND, 16, sr, concat);
-    BwdPlan p;
-    rc = bwd_plan(prec, T, B, H, ND, a, p);
-    if (rc) return rc;
-    const int NB = p.NB, NC = p.NC, K4p = p.K4p;
-    a.wdirect = p.wdirect ? 1 : 0;
-    a.tw = tw;
-    const size_t lds = p.lds;
+    LAS_CHECK_ARG(prec == LAS_PREC_BF16 || prec == LAS_PREC_F32);
+    BwdPlan p = plan_bwd(prec, T, B, H, ND, sr, concat);
+    if (p.rc) return p.rc;
+    p.a.tw = dgf_bf16;
     hipStream_t st = (hipStream_t)stream;
-    const bool ring_behind = p.gr && (char*)dgx == (char*)sync + sizeof(SyncWords);      // one fill for both
-    LAS_HIP(hipMemsetAsync(sync, 0, sizeof(SyncWords) + (ring_behind ? p.ws : 0), st));
-    if (p.gr) {
-        *tw_done = true;
-        if (!ring_behind) LAS_HIP(hipMemsetAsync(dgx, 0, p.ws, st));      // tags of earlier launches must not match
-#define LAS_GR_GO(N_, M_)                                                                                              \
-    {                                                                                                                 \
-        auto k = lstm_bwd_gr_kernel<N_, M_, (M_ > 8 ? 12 : 4)>;                                                                          \
-        LAS_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));           \
-        hipLaunchKernelGGL(k, dim3(lstm_grid(a)), dim3(NT + 64), lds, st, a, dy, gates, cs, w_hh, lens, (u32x4*)dgx, dgf, \
-                           (SyncWords*)sync, status);                                                                 \
-        LAS_LAUNCH_OK();                                                                                              \
-        return LAS_OK;                                                                                                \
-    }
-        const int mt = (a.G + 3) / 4;
-        if (NB == 1) { if (mt <= 5) LAS_GR_GO(1, 5) else if (mt <= 8) LAS_GR_GO(1, 8) else LAS_GR_GO(1, 16) }
-        else { if (mt <= 5) LAS_GR_GO(2, 5) else LAS_GR_GO(2, 8) }
-#undef LAS_GR_GO
-    }
-    if (p.f32w) {
-#define LAS_F32W_BWD(N_, M_)                                                                                            \
-    {                                                                                                                 \
-        auto k = lstm_bwd_f32w_kernel<N_, M_>;                                                                        \
-        LAS_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));           \
-        hipLaunchKernelGGL(k, dim3(lstm_grid(a)), dim3(NT), lds, st, a, dy, gates, cs, w_hh, lens, (unsigned*)dgx, dgf, \
-                           (SyncWords*)sync, status);                                                                 \
-        LAS_LAUNCH_OK();                                                                                              \
-        return LAS_OK;                                                                                                \
-    }
-        const int mt = (a.G + 3) / 4;
-        if (NB == 1) { if (mt <= 8) LAS_F32W_BWD(1, 8) else if (mt <= 12) LAS_F32W_BWD(1, 12) else LAS_F32W_BWD(1, 16) }
-        else { if (mt <= 8) LAS_F32W_BWD(2, 8) else if (mt <= 12) LAS_F32W_BWD(2, 12) else LAS_F32W_BWD(2, 16) }
-#undef LAS_F32W_BWD
-    }
-    if (p.ks) {
-#define LAS_KS_GO(P_, N_, M_)                                                                                          \
-    {                                                                                                                 \
-        auto k = lstm_bwd_ks_kernel<P_, N_, M_>;                                                                      \
-        LAS_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));           \
-        hipLaunchKernelGGL(k, dim3(lstm_grid(a)), dim3(NT), lds, st, a, dy, gates, cs, w_hh, lens, (unsigned*)dgx, dgf, \
-                           (SyncWords*)sync, status);                                                                 \
-        LAS_LAUNCH_OK();                                                                                              \
-        return LAS_OK;                                                                                                \
-    }
-        const int mt = (a.G + 3) / 4;
-        if (prec == LAS_PREC_BF16) {
-            if (NB == 1) { if (mt <= 5) LAS_KS_GO(LAS_PREC_BF16, 1, 5) else if (mt <= 8) LAS_KS_GO(LAS_PREC_BF16, 1, 8) else LAS_KS_GO(LAS_PREC_BF16, 1, 16) }
-            else { if (mt <= 5) LAS_KS_GO(LAS_PREC_BF16, 2, 5) else if (mt <= 8) LAS_KS_GO(LAS_PREC_BF16, 2, 8) else LAS_KS_GO(LAS_PREC_BF16, 2, 16) }
-        } else { if (NB == 1) LAS_KS_GO(LAS_PREC_F32, 1, 1) else LAS_KS_GO(LAS_PREC_F32, 2, 1) }
-#undef LAS_KS_GO
-    }
-#define LAS_BWD_ARGS a, NC, K4p, lds, st, dy, gates, cs, w_hh, lens, dgx, dgf, (SyncWords*)sync, status
-    if (prec == LAS_PREC_BF16) {
-        const int kq = K4p / 32 / 4;                        // k-steps per wave
-        const bool direct = NB <= 2 && NC == 1 && !LAS_AB_KNOB("LAS_LSTM_NO_DIRECT");
-        if (direct && kq == 8)  { LAS_NB_SWITCH(NB, return (launch_bwd<LAS_PREC_BF16, NB_ <= 2 ? NB_ : 1, 8>(LAS_BWD_ARGS))); }
-        if (direct && kq == 10) { LAS_NB_SWITCH(NB, return (launch_bwd<LAS_PREC_BF16, NB_ <= 2 ? NB_ : 1, 10>(LAS_BWD_ARGS))); }
-        if (direct && kq == 16 && NB == 1) { return launch_bwd<LAS_PREC_BF16, 1, 16>(LAS_BWD_ARGS); }
-        LAS_NB_SWITCH(NB, return (launch_bwd<LAS_PREC_BF16, NB_, 0>(LAS_BWD_ARGS)));
-    } else {
-        LAS_NB_SWITCH(NB, return (launch_bwd<LAS_PREC_F32, NB_, 0>(LAS_BWD_ARGS)));
-    }
-#undef LAS_BWD_ARGS
-    return LAS_E_BADARG;
+    int rc = zero_sync_and_ring(sync, dgx, p.fill, st);
+    if (rc == LAS_OK) rc = p.row->launch(p, BwdIo{dy, gates, cs, w_hh, lens, {dgx}, dgf, (SyncWords*)sync, status}, st);
+    if (rc == LAS_OK && dgf_bf16 && !p.twin) rc = las_cast_bf16(dgf, dgf_bf16, (int64_t)T * B * ND * 4 * H, stream);
+    return rc;
 }

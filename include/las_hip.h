@@ -92,11 +92,17 @@ int las_colsum2(const float* X, int64_t ld, int M, int N, float beta, float* out
  * Limits: H % 2 == 0, B <= 2048 (the batch is cut into independent slices of <= 128 rows, normally ~12), ND*ceil(H/16) <= 256 (one workgroup per CU, all co-resident). */
 void las_lstm_out_shape(int T, int H, int ND, int sr, int concat, int* T_out, int* F_out);
 size_t las_lstm_sync_bytes(void);
-size_t las_lstm_hx_bytes(int prec, int T, int B, int H, int ND);        /* size of the `hx` exchange workspace of rec_fwd */
+size_t las_lstm_hx_bytes(int prec, int T, int B, int H, int ND);        /* size of the `hx` exchange workspace of rec_fwd: room for either ring of the geometry, also for shapes rec_fwd then refuses */
 size_t las_lstm_bwd_ws_bytes(int prec, int T, int B, int H, int ND);   /* size of the `dgx` exchange workspace of rec_bwd */
-int las_lstm_bwd_is_ksplit(int prec, int T, int B, int H, int ND);     /* which kernel rec_bwd runs: 3 lstm_bwd_x32_kernel (512 < H <= 1024: 32 units per workgroup, every group inside one XCD), 2 lstm_bwd_gr_kernel (reduce-scatter of partial dh in tagged granules), 1 lstm_bwd_ks_kernel (the same behind a flag), 0 lstm_bwd_kernel (all-gather of dgates) */
-int las_lstm_fwd_variant(int prec, int T, int B, int H, int ND);       /* which kernel rec_fwd runs: 2 lstm_fwd_x32_kernel (512 < H <= 1024, 32 units per workgroup), 1 lstm_fwd_gr_kernel (tagged granules), 0 lstm_fwd_kernel */
-int las_lstm_resident_wgs(int prec, int T, int B, int H, int ND);      /* workgroups rec_fwd / rec_bwd keep resident for the whole launch (one per CU, all must be co-resident); callers that overlap other device work with the recurrence (RCCL collectives: dist.py) use it to decide whether that work finds free CUs */
+int las_lstm_bwd_is_ksplit(int prec, int T, int B, int H, int ND);     /* which kernel rec_bwd runs: 3 lstm_bwd_x32_kernel (512 < H <= 1024: 32 units per workgroup, every group inside one XCD), 2 lstm_bwd_gr_kernel (reduce-scatter of partial dh in tagged granules), 1 lstm_bwd_ks_kernel (the same behind a flag) and its fp32 stand-in lstm_bwd_f32w_kernel, 0 lstm_bwd_kernel (all-gather of dgates) or an unsupported shape */
+int las_lstm_fwd_variant(int prec, int T, int B, int H, int ND);       /* which kernel rec_fwd runs: 2 lstm_fwd_x32_kernel (512 < H <= 1024, 32 units per workgroup), 1 lstm_fwd_gr_kernel (tagged granules), 0 lstm_fwd_kernel, its fp32 stand-in lstm_fwd_f32w_kernel, or an unsupported shape */
+int las_lstm_resident_wgs(int prec, int T, int B, int H, int ND);      /* workgroups rec_bwd keeps resident for the whole launch (one per CU, all must be co-resident): the groups of the 16-unit geometry, or of the 32-unit one where the shape takes it.  rec_fwd keeps the same number except at H = 512 without XCD grouping, where its 8-unit slices make it up to twice as many (LAS_LSTM_NO_XL, ND = 2, B = 8: 128 here, 256 in the forward grid).  Callers that overlap other device work with the backward recurrence (RCCL collectives: dist.py) use it to decide whether that work finds free CUs */
+/* The plan rec_fwd (backward = 0; I > 0: rec_fwd_fx with that input width) or rec_bwd follows for a shape, as one line in buf:
+ * "<kernel instance> grid=G block=N lds=BYTES fill=BYTES ws=BYTES twin=0|1" -- fill: bytes of the exchange ring the launch zeroes,
+ * ws: what las_lstm_hx_bytes / las_lstm_bwd_ws_bytes ask for, twin: the kernel writes the bf16 twin itself.  Returns what the launch
+ * would return from planning (LAS_OK, else the instance is "-"); touches no device, reads the fallback switches like a launch. */
+int las_lstm_plan_describe(int prec, int T, int B, int H, int ND, int sr, int concat, int I /*0: no fused input*/,
+                           int backward, char* buf, size_t cap);
 /* y_bf16 / dgf_bf16 (may be null): bf16 twins of y [T_out][B][F_out] / dgf [T][B][ND*4H], the operands of the GEMMs behind the
  * launch (projection; d x, d W_ih, d W_hh).  The granule and 32-unit kernels write them next to the fp32 stores; behind the
  * other kernels the call appends one cast pass. */

@@ -61,6 +61,22 @@ class FlatParams:
         module.n_params = sum(math.prod(s) for _, s in self.specs)
 
 
+def merge_ranges(entries, total):
+    """Sorted (offset, count) list of flat-vector ranges with adjacent entries merged into one; ValueError for an empty,
+    overlapping or out-of-bounds entry (bounds: [0, total))."""
+    out = []
+    for off, cnt in sorted((int(o), int(c)) for o, c in entries):
+        if cnt <= 0 or off < 0 or off + cnt > int(total):
+            raise ValueError('range (%d, %d) is outside the flat vector of %d elements' % (off, cnt, total))
+        if out and off < out[-1][0] + out[-1][1]:
+            raise ValueError('range (%d, %d) overlaps (%d, %d)' % ((off, cnt) + out[-1]))
+        if out and off == out[-1][0] + out[-1][1]:
+            out[-1] = (out[-1][0], out[-1][1] + cnt)
+        else:
+            out.append((off, cnt))
+    return out
+
+
 def param_shapes(example_input, output_dim, model_para):
     """{reference parameter name: shape} of the architecture a YAML describes (no device needed)."""
     class _Probe(Seq2Seq):
@@ -177,6 +193,17 @@ class Seq2Seq(nn.Module):
         each encoder layer's BPTT node with its first gradient view), in the order backward fires them: top layer first.
         dist.exchange_without_backward replays them on a rank that has no backward to run."""
         return [self.param_slices[f'encoder.layer{l}.layer.weight_ih_l0'][0] for l in reversed(range(len(self.dims)))]
+
+    def noise_ranges(self):
+        """Device int64 table [R][2] of (offset, count) into the flat vectors: what weight noise perturbs (ops.weight_noise_apply)
+        -- every parameter with dim() >= 2 (weight matrices, conv filters, the embedding), no bias, no alignment padding;
+        adjacent entries merged, bounds checked, built once."""
+        if getattr(self, '_noise_ranges', None) is None:
+            rows = merge_ranges([(off, k) for off, k, shape in self.param_slices.values() if len(shape) >= 2],
+                                self.flat_params.numel())
+            self._noise_count = sum(c for _, c in rows)               # elements noised (the kernels' byte counts)
+            self._noise_ranges = torch.tensor(rows, dtype=torch.int64, device=self.flat_params.device).view(-1, 2)
+        return self._noise_ranges
 
     def sync_bf16(self):
         """Refresh the weights' bf16 shadow after the fp32 weights were written by anything but the fused optimiser."""

@@ -867,6 +867,58 @@ def joint_loss(att_pred, ctc_pred, y, ntok, enc_len, L, w, label_smoothing=0.0, 
     return JointLossFn.apply(att_pred, ctc_pred, y, ntok, enc_len, L, float(w), label_smoothing, prior)
 
 
+# ----------------------------------------------------------------------------- weight noise
+def check_noise_sigma(sigma):
+    """float(sigma) if it is a finite number >= 0, ValueError otherwise."""
+    try:
+        s = float(sigma)
+    except (TypeError, ValueError):
+        raise ValueError('weight noise std must be a number >= 0, got %r' % (sigma,))
+    if not 0.0 <= s < float('inf'):
+        raise ValueError('weight noise std must be a finite number >= 0, got %r' % (sigma,))
+    return s
+
+
+_U64, _U32 = __import__('ctypes').c_uint64, __import__('ctypes').c_uint32
+
+
+def weight_noise_apply(model, sigma, seed, step):
+    """flat_params (and the bf16 shadow) <- W + sigma * z(seed, step, flat index) on model.noise_ranges(), the clean W stashed in
+    model.flat_clean (allocated here on first use, never read before this call has written it): las_weight_noise_apply, one
+    launch on the current stream.  Every call must be followed by weight_noise_restore before the weights are updated, saved or
+    evaluated; a second apply before that raises (it would stash noisy weights)."""
+    sigma = check_noise_sigma(sigma)
+    if getattr(model, '_noise_applied', False):
+        raise _lib.LasError('weight_noise_apply: the weights are already noisy (no weight_noise_restore since the last apply)')
+    tab = model.noise_ranges()
+    p = model.flat_params
+    if getattr(model, 'flat_clean', None) is None:
+        model.flat_clean = torch.empty(p.shape, dtype=torch.float32, device=p.device)
+    p16 = getattr(model, 'flat_params16', None)
+    with _Timed('weight_noise_kernel<true>', 14.0 * model._noise_count, 'B', single=True):
+        check(_lib.lib().las_weight_noise_apply(ptr(p), ptr(p16), ptr(model.flat_clean), LL(p.numel()), ptr(tab), I(tab.shape[0]),
+                                                F(sigma), _U64(int(seed) & 0xffffffffffffffff), _U32(int(step) & 0xffffffff),
+                                                cur_stream()), 'las_weight_noise_apply')
+    model._noise_applied = True
+
+
+def weight_noise_restore(model):
+    """Puts the clean weights (and their bf16 shadow) back: las_weight_noise_restore on the current stream, which first waits for
+    the tail of every side stream -- no kernel that reads a weight may still be running when the weights change back."""
+    if not getattr(model, '_noise_applied', False):
+        raise _lib.LasError('weight_noise_restore without a preceding weight_noise_apply')
+    cur = torch.cuda.current_stream()
+    for s in side_streams():
+        cur.wait_stream(s)
+    join_side_stream()
+    p, tab = model.flat_params, model.noise_ranges()
+    p16 = getattr(model, 'flat_params16', None)
+    with _Timed('weight_noise_kernel<false>', 10.0 * model._noise_count, 'B', single=True):
+        check(_lib.lib().las_weight_noise_restore(ptr(p), ptr(p16), ptr(model.flat_clean), LL(p.numel()), ptr(tab),
+                                                  I(tab.shape[0]), cur_stream()), 'las_weight_noise_restore')
+    model._noise_applied = False
+
+
 # ----------------------------------------------------------------------------- metrics
 def argmax_rows(logits):
     """int32 argmax over the last dim of a contiguous fp32 tensor [..., V]."""

@@ -44,6 +44,18 @@ def label_smoothing_config(config):
     return eps, kind
 
 
+def weight_noise_config(config):
+    """asr_model.optimizer.weight_noise_std (finite float >= 0, default 0 = off) and .weight_noise_start (int >= 0, default 0:
+    noise is active on steps >= it) -> (std, start); ValueError for anything else.  Gaussian weight noise: the step's gradient
+    is taken at W + N(0, std^2) and applied to the clean W.  Not in the reference."""
+    opt = config['asr_model']['optimizer']
+    std = ops.check_noise_sigma(opt.get('weight_noise_std', 0.0))
+    start = opt.get('weight_noise_start', 0)
+    if isinstance(start, bool) or not isinstance(start, int) or start < 0:
+        raise ValueError('weight_noise_start must be an integer >= 0, got %r' % (start,))
+    return std, start
+
+
 class ScalarLog:
     """SummaryWriter-shaped sink: add_scalars / add_text / add_image."""
 
@@ -130,6 +142,7 @@ class Trainer(Solver):
         self._pending = None
         self.label_smoothing, self.ls_prior_kind = label_smoothing_config(config)
         self.ls_prior = None             # device fp32 [V] for 'unigram' (set_model); None = uniform
+        self.weight_noise_std, self.weight_noise_start = weight_noise_config(config)
         self.len_stream = True           # length inference + its D2H on a stream of their own (train_step; tests switch it off)
 
     # ------------------------------------------------------------------------------------------------ data
@@ -165,6 +178,8 @@ class Trainer(Solver):
             self.best_val_ed = float(ck.get('best_val_ed', 2.0))
         ldist.broadcast_params(self.asr_model.flat_params)
         self.asr_model.sync_bf16()
+        if self.weight_noise_std > 0:
+            self.asr_model.noise_ranges()                                     # (its H2D copy happens here, not in a step)
 
     # ------------------------------------------------------------------------------------------------ one step
     def train_step(self, x, y, tf_rate, host_lens=None, shard_weight=1.0, inputs_ready=None):
@@ -208,16 +223,25 @@ class Trainer(Solver):
                 state_len, ans_len = host[:-1], int(host[-1])
             else:
                 state_len, ans_len = list(host_lens[0]), int(host_lens[1])
-        self.asr_model.ctc_branch = True                          # CTC head + loss beside the attend-and-spell loops (ops.branch_stream)
+        # weight noise: forward and backward see W + N(0, std^2) -- the same draw on every rank, a function of (seed, step, index)
+        # -- and the clean W is back (bf16 shadow included) before the update, also when anything in between raises
+        noisy = self.weight_noise_std > 0 and self.step >= self.weight_noise_start
+        if noisy:
+            ops.weight_noise_apply(self.asr_model, self.weight_noise_std, self.paras.seed, self.step)
         try:
-            ctc_pred, enc_len, att_pred, _ = self.asr_model(x, ans_len, tf_rate=tf_rate, teacher=y, state_len=state_len,
-                                                             state_len_dev=lens)
+            self.asr_model.ctc_branch = True                      # CTC head + loss beside the attend-and-spell loops (ops.branch_stream)
+            try:
+                ctc_pred, enc_len, att_pred, _ = self.asr_model(x, ans_len, tf_rate=tf_rate, teacher=y, state_len=state_len,
+                                                                 state_len_dev=lens)
+            finally:
+                self.asr_model.ctc_branch = False
+            # (label smoothing is a training regulariser: valid() keeps the plain loss, so dev losses stay comparable between runs)
+            loss, att_loss, ctc_loss = ops.joint_loss(att_pred, ctc_pred, y, ntok, self.asr_model.last_enc_len_dev, ans_len,
+                                                      self.ctc_weight, label_smoothing=self.label_smoothing, prior=self.ls_prior)
+            ldist.backward_with_overlap(loss if shard_weight == 1.0 else loss * shard_weight, self.asr_model)   # solver.py:177
         finally:
-            self.asr_model.ctc_branch = False
-        # (label smoothing is a training regulariser: valid() keeps the plain loss, so dev losses stay comparable between runs)
-        loss, att_loss, ctc_loss = ops.joint_loss(att_pred, ctc_pred, y, ntok, self.asr_model.last_enc_len_dev, ans_len,
-                                                  self.ctc_weight, label_smoothing=self.label_smoothing, prior=self.ls_prior)
-        ldist.backward_with_overlap(loss if shard_weight == 1.0 else loss * shard_weight, self.asr_model)   # solver.py:177
+            if noisy:
+                ops.weight_noise_restore(self.asr_model)
         self.asr_opt.step(zero_grad=True)                         # clip 5, NaN guard, update (solver.py:178-182)
         return loss, att_loss, ctc_loss, att_pred, ans_len
 

@@ -299,6 +299,25 @@ int las_adam_step(float* p, float* g, float* m, float* v, int64_t n, float lr, f
 int las_adadelta_step(float* p, float* g, float* sq, float* acc, int64_t n, float lr, float rho, float eps,
                       const float* norm3, int zero_grad, void* p_bf16, void* stream);
 
+/* ---- Gaussian weight noise over ranges of the flat parameter vector (csrc/noise.hip) -----------------------------
+ * NOT in the reference (src/solver.py:127-182 takes the gradient at the weights it updates): one step evaluates the gradient
+ * at W + N(0, sigma^2) and applies it to the clean W.  ranges: DEVICE int64 [R][2] = (offset, count) into the flat vector
+ * (NULL: the one range (0, n)); every index i inside a range is touched, nothing outside any range is read or written in
+ * any of the three buffers.
+ *   apply:   clean[i] = p[i];  p[i] = p[i] + sigma*z(i) (an fp32 multiply, then an fp32 add);  p_bf16[i] = bf16(p[i]) (RNE)
+ *   restore: p[i] = clean[i] bit for bit;  p_bf16[i] = bf16(clean[i])
+ * z(i) depends on (seed, step, i) only -- not on the grid, the range table or the precision mode:
+ *   (x0,x1,x2,x3) = Philox4x32-10(counter = (g & 0xffffffff, g >> 32, step, 0), key = (seed & 0xffffffff, seed >> 32)),
+ *   g = i >> 2; the four words serve elements 4g .. 4g+3;   u(x) = ((x >> 9) + 0.5f) * 2^-23  (exact, in [2^-24, 1 - 2^-24]);
+ *   r = sqrt(-2 ln u(x0)), z0 = r cos(2 pi u(x1)), z1 = r sin(2 pi u(x1)); z2, z3 the same from (x2, x3).  |z| <= sqrt(48 ln 2).
+ * p, p_bf16 (may be NULL) and clean are 16-byte aligned bases of n elements.  LAS_E_BADARG: a null or misaligned base,
+ * n <= 0, a table with R <= 0, sigma < 0 or NaN.  One launch per call, whatever R is. */
+int las_weight_noise_apply(float* p, void* p_bf16 /* may be NULL */, float* clean, int64_t n,
+                           const int64_t* ranges /* device, [R][2] = (offset, count) */, int R,
+                           float sigma, uint64_t seed, uint32_t step, void* stream);
+int las_weight_noise_restore(float* p, void* p_bf16 /* may be NULL */, const float* clean, int64_t n,
+                             const int64_t* ranges, int R, void* stream);
+
 /* Weight operand of a skinny product (las_skinny_linear / las_lstm_cell_fwd / the decoder's per-step products) packed as
  * bf16 MFMA fragments: for every block of 16 output rows and every 32-wide k-step over the concatenated segments,
  * 64 lanes x 8 values; cell_mode: rows are the gate-interleaved rows of las_lstm_cell_fwd (N = 4C). */

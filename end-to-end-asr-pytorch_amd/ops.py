@@ -919,6 +919,67 @@ def weight_noise_restore(model):
     model._noise_applied = False
 
 
+# ----------------------------------------------------------------------------- weight averaging (EMA)
+def check_ema_decay(decay):
+    """float(decay) if it is a number in [0, 1) (no bool), ValueError otherwise."""
+    if isinstance(decay, bool):
+        raise ValueError('ema decay must be a number in [0, 1), got %r' % (decay,))
+    try:
+        d = float(decay)
+    except (TypeError, ValueError):
+        raise ValueError('ema decay must be a number in [0, 1), got %r' % (decay,))
+    if not 0.0 <= d < 1.0:                                    # (false for NaN)
+        raise ValueError('ema decay must be in [0, 1), got %r' % (decay,))
+    return d
+
+
+def ema_decay_at(k, decay):
+    """The decay of the k-th update after the initialising copy (k >= 1): min(decay, (1 + k)/(10 + k)), the usual warm-up -- a
+    late ema_start or a short run is not dominated by its first iterate."""
+    k = int(k)
+    if k < 1:
+        raise ValueError('ema_decay_at: k counts the updates after the initialising copy, k >= 1, got %r' % (k,))
+    return min(float(decay), (1.0 + k) / (10.0 + k))
+
+
+def ema_update(model, decay, init):
+    """model.flat_ema <- decay*flat_ema + (1 - decay)*flat_params, or, with init, <- flat_params (flat_ema is allocated here on
+    first use and is not read by an initialising call): las_ema_update, one launch on the current stream.  The average must
+    only ever see clean, live weights: raises while the model is swapped (ema_swap) or noisy (weight_noise_apply)."""
+    decay = check_ema_decay(decay)
+    if getattr(model, '_ema_swapped', False):
+        raise _lib.LasError('ema_update: the live weights are swapped out (no second ema_swap since the last one)')
+    if getattr(model, '_noise_applied', False):
+        raise _lib.LasError('ema_update: the weights are noisy (no weight_noise_restore since the last apply)')
+    p = model.flat_params
+    if getattr(model, 'flat_ema', None) is None:
+        if not init:
+            raise _lib.LasError('ema_update: the first update of an average must be the initialising one')
+        model.flat_ema = torch.empty(p.shape, dtype=torch.float32, device=p.device)
+    with _Timed('ema_update_kernel<%s>' % ('true' if init else 'false'), (8.0 if init else 12.0) * p.numel(), 'B', single=True):
+        check(_lib.lib().las_ema_update(ptr(model.flat_ema), ptr(p), LL(p.numel()), F(decay), I(1 if init else 0), cur_stream()),
+              'las_ema_update')
+
+
+def ema_swap(model):
+    """Exchanges flat_params and flat_ema (the bf16 shadow rewritten from the new flat_params) and toggles model._ema_swapped:
+    las_ema_swap on the current stream, which first waits for the tail of every side stream, as weight_noise_restore does -- no
+    kernel that reads a weight may still be running when the weights change.  Its own inverse."""
+    if getattr(model, 'flat_ema', None) is None:
+        raise _lib.LasError('ema_swap: there is no average yet (no ema_update so far)')
+    if getattr(model, '_noise_applied', False):
+        raise _lib.LasError('ema_swap: the weights are noisy (no weight_noise_restore since the last apply)')
+    cur = torch.cuda.current_stream()
+    for s in side_streams():
+        cur.wait_stream(s)
+    join_side_stream()
+    p = model.flat_params
+    p16 = getattr(model, 'flat_params16', None)
+    with _Timed('ema_swap_kernel', (18.0 if p16 is not None else 16.0) * p.numel(), 'B', single=True):
+        check(_lib.lib().las_ema_swap(ptr(p), ptr(p16), ptr(model.flat_ema), LL(p.numel()), cur_stream()), 'las_ema_swap')
+    model._ema_swapped = not getattr(model, '_ema_swapped', False)
+
+
 # ----------------------------------------------------------------------------- metrics
 def argmax_rows(logits):
     """int32 argmax over the last dim of a contiguous fp32 tensor [..., V]."""

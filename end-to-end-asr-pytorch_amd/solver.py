@@ -56,6 +56,19 @@ def weight_noise_config(config):
     return std, start
 
 
+def ema_config(config):
+    """asr_model.optimizer.ema_decay (float in [0, 1), default 0 = off) and .ema_start (int >= 0, default 0: the average is
+    initialised by copy after the update of step == ema_start) -> (decay, start); ValueError for anything else.  An exponential
+    moving average of the weights, which validation, the best checkpoint and decoding then use.  Not in the reference
+    (DESIGN.md §3.11, §8)."""
+    opt = config['asr_model']['optimizer']
+    decay = ops.check_ema_decay(opt.get('ema_decay', 0.0))
+    start = opt.get('ema_start', 0)
+    if isinstance(start, bool) or not isinstance(start, int) or start < 0:
+        raise ValueError('ema_start must be an integer >= 0, got %r' % (start,))
+    return decay, start
+
+
 class ScalarLog:
     """SummaryWriter-shaped sink: add_scalars / add_text / add_image."""
 
@@ -143,6 +156,7 @@ class Trainer(Solver):
         self.label_smoothing, self.ls_prior_kind = label_smoothing_config(config)
         self.ls_prior = None             # device fp32 [V] for 'unigram' (set_model); None = uniform
         self.weight_noise_std, self.weight_noise_start = weight_noise_config(config)
+        self.ema_decay, self.ema_start = ema_config(config)
         self.len_stream = True           # length inference + its D2H on a stream of their own (train_step; tests switch it off)
 
     # ------------------------------------------------------------------------------------------------ data
@@ -176,6 +190,11 @@ class Trainer(Solver):
                 self.asr_opt.load_state_dict(ck['opt'])
             self.step = int(ck.get('step', 0))
             self.best_val_ed = float(ck.get('best_val_ed', 2.0))
+            if self.ema_decay > 0 and 'ema' in ck:                            # (absent: initialised at the next update)
+                m = self.asr_model
+                m.flat_ema = torch.zeros_like(m.flat_params)
+                for name, (off, k, _) in m.param_slices.items():
+                    m.flat_ema[off:off + k].copy_(ck['ema'][name].to(self.device, torch.float32).reshape(-1))
         ldist.broadcast_params(self.asr_model.flat_params)
         self.asr_model.sync_bf16()
         if self.weight_noise_std > 0:
@@ -198,6 +217,7 @@ class Trainer(Solver):
         if x.shape[0] == 0:                                       # a bucket smaller than the world: nothing on this rank,
             ldist.exchange_without_backward(self.asr_model)       # but it joins the exchange (the SAME collective sequence as
             self.asr_opt.step(zero_grad=True)                     # its peers' backward issues) and the (global) update
+            self._ema_after_update()                              # (the same update, so the same average)
             z = torch.zeros((), device=self.device)
             return z, z, z, None, 0
         if inputs_ready is not None and inputs_ready is not True:
@@ -243,7 +263,22 @@ class Trainer(Solver):
             if noisy:
                 ops.weight_noise_restore(self.asr_model)
         self.asr_opt.step(zero_grad=True)                         # clip 5, NaN guard, update (solver.py:178-182)
+        self._ema_after_update()
         return loss, att_loss, ctc_loss, att_pred, ans_len
+
+    def _ema_after_update(self):
+        """The one place the weight average moves: behind the optimiser's update of the clean weights (any weight noise has been
+        restored by then).  The decay is a function of the host's step count alone -- the average also moves on a step the
+        device-side NaN guard skipped -- so every rank computes the same average with no collective and no read-back."""
+        if self.ema_decay <= 0:
+            return
+        u = self.step - self.ema_start
+        if u < 0:
+            return
+        if u == 0 or getattr(self.asr_model, 'flat_ema', None) is None:   # (None: a resumed run that raised ema_start, or whose
+            ops.ema_update(self.asr_model, self.ema_decay, True)          # checkpoint has no average)
+        else:
+            ops.ema_update(self.asr_model, ops.ema_decay_at(u, self.ema_decay), False)
 
     def exec(self):
         self.verbose('Training set total ' + str(len(self.train_set)) + ' batches.')
@@ -357,13 +392,21 @@ class Trainer(Solver):
         """Greedy-decoding validation, reference solver.py:211-291: eval mode for its duration
         (solver.py:211,287: no Speller dropout), no-teacher argmax feedback for ans_len + VAL_STEP steps, dev losses,
         error rate / accuracy, attention maps + hypotheses + references of the LAST bucket (solver.py:266-276), best
-        checkpoint + best_hyp.txt."""
-        was_training = self.asr_model.training
-        self.asr_model.eval()
+        checkpoint + best_hyp.txt.  When a weight average exists (ema_decay > 0, from ema_start on) it is swapped in for the
+        duration: losses, error rate, attention maps, best_hyp.txt and the best-checkpoint decision are the average's."""
+        averaged = getattr(self.asr_model, 'flat_ema', None) is not None
+        if averaged:
+            ops.ema_swap(self.asr_model)
         try:
-            self._valid_body()
+            was_training = self.asr_model.training
+            self.asr_model.eval()
+            try:
+                self._valid_body()
+            finally:
+                self.asr_model.train(was_training)
         finally:
-            self.asr_model.train(was_training)
+            if averaged:
+                ops.ema_swap(self.asr_model)
 
     def _valid_body(self):
         val_ctc = val_att = val_acc = val_cer = 0.0
@@ -421,9 +464,20 @@ class Trainer(Solver):
                         f.write(t1 + ',' + t2 + '\n')
 
     def save_checkpoint(self, path):
-        sd = {k: v.detach().clone() for k, v in self.asr_model.named_parameters()}
-        torch.save({'model': sd, 'opt': self.asr_opt.state_dict(), 'step': self.step, 'best_val_ed': self.best_val_ed,
-                    'config': json.dumps(self.config['asr_model'])}, path)
+        """'model' is always the live weights (the optimiser's moments belong to those); when a weight average exists, 'ema' is
+        the average under the same names and 'ema_decay' its decay -- whichever of the two flat_params holds at the moment
+        (valid() saves the best checkpoint while the average is swapped in)."""
+        m = self.asr_model
+        ck = {'opt': self.asr_opt.state_dict(), 'step': self.step, 'best_val_ed': self.best_val_ed,
+              'config': json.dumps(self.config['asr_model'])}
+        if getattr(m, 'flat_ema', None) is None:
+            ck['model'] = {k: v.detach().clone() for k, v in m.named_parameters()}
+        else:
+            live, ema = (m.flat_ema, m.flat_params) if getattr(m, '_ema_swapped', False) else (m.flat_params, m.flat_ema)
+            for key, flat in (('model', live), ('ema', ema)):
+                ck[key] = {k: flat[off:off + n].view(shape).detach().clone() for k, (off, n, shape) in m.param_slices.items()}
+            ck['ema_decay'] = self.ema_decay
+        torch.save(ck, path)
 
 
 class Tester(Solver):
@@ -462,15 +516,18 @@ class Tester(Solver):
             self.sample_x = self.sample_x[0]
 
     def set_model(self):
-        """Load the saved ASR (state_dict checkpoint written by Trainer.save_checkpoint)."""
+        """Load the saved ASR (state_dict checkpoint written by Trainer.save_checkpoint): its averaged weights ('ema') when the
+        run kept an average, unless solver.decode_ema is false (not in the reference)."""
         path = os.path.join(self.ckpdir, 'asr')
         self.verbose('Load ASR model from ' + path)
         ck = torch.load(path, map_location=self.device, weights_only=True)
         mp = json.loads(ck['config']) if 'config' in ck else self.config['asr_model']
         self.asr_model = Seq2Seq(self.sample_x, self.mapper.get_dim(), mp, device=self.device)
-        self.asr_model.load_reference_state(ck['model'])
-        self.ctc_weight = mp['optimizer']['joint_ctc']
         s = self.config['solver']
+        which = 'ema' if 'ema' in ck and s.get('decode_ema', True) else 'model'   # the weight average, when the run kept one
+        self.verbose("Decoding with the checkpoint's " + ('averaged (ema) weights' if which == 'ema' else 'weights'))
+        self.asr_model.load_reference_state(ck[which])
+        self.ctc_weight = mp['optimizer']['joint_ctc']
         dcw = s.get('decode_ctc_weight', 0)
         if dcw > 0:                                   # solver.py:317-323
             assert self.asr_model.joint_ctc, 'The ASR was not trained with CTC'

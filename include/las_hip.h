@@ -318,6 +318,21 @@ int las_weight_noise_apply(float* p, void* p_bf16 /* may be NULL */, float* clea
 int las_weight_noise_restore(float* p, void* p_bf16 /* may be NULL */, const float* clean, int64_t n,
                              const int64_t* ranges, int R, void* stream);
 
+/* ---- Exponential moving average of the flat parameter vector (csrc/ema.hip) ----------------------------------------
+ * NOT in the reference (its validation, checkpoints and decoding use the raw iterate).  Launches of their own behind the
+ * optimiser's; las_adam_step / las_adadelta_step do not know the average exists.
+ *   update, init != 0: ema[i] = p[i] for i < n; ema is NOT read (it may hold anything, NaN included)
+ *   update, init == 0: ema[i] = decay*ema[i] + (1.f - decay)*p[i] in fp32 in exactly that order: (1.f - decay) formed once,
+ *                      two products, one sum, no contraction -- defined bit for bit
+ *   swap:              p[i] <-> ema[i] bit for bit (NaN payloads included); p_bf16[i] = bf16(new p[i]) (RNE, as the optimiser
+ *                      kernels write the shadow); its own inverse
+ * p is never written by update.  No element at an index >= n is read or written in any buffer.  ema, p and p_bf16 (may be
+ * NULL) are 16-byte aligned bases of n elements.  LAS_E_BADARG: a null or misaligned base, n <= 0 or n > 2^40 (one float4
+ * group per lane: more blocks than a grid holds), decay outside [0, 1) or NaN (also with init).  One launch per call: update
+ * 12 B per element (8 with init), swap 18 B (16 without a shadow). */
+int las_ema_update(float* ema, const float* p, int64_t n, float decay, int init, void* stream);
+int las_ema_swap(float* p, void* p_bf16 /* may be NULL */, float* ema, int64_t n, void* stream);
+
 /* Weight operand of a skinny product (las_skinny_linear / las_lstm_cell_fwd / the decoder's per-step products) packed as
  * bf16 MFMA fragments: for every block of 16 output rows and every 32-wide k-step over the concatenated segments,
  * 64 lanes x 8 values; cell_mode: rows are the gate-interleaved rows of las_lstm_cell_fwd (N = 4C). */
